@@ -27,6 +27,14 @@ only collective; pairs are sharded, scaling is weak).
 
 Launch: ``python bench.py [--gpus N --steps K --warmup W]``; for N>1 under
 ``torch.distributed.run`` (one process per GPU, RCCL).  Rank 0 prints ONE JSON line.
+
+A plain run does what the headline needs and no more: set-up, warmup, the K timed steps, the
+result line (``value``, ``ms_per_step``, and the roofline fields that come from the timed steps'
+own HIP events).  ``--full`` adds the legs that take runs of their own: the host-buffer API rate
+(``pcie_inclusive``), the CPU baseline (``cpu_baseline``) and the oracle re-check of the scores
+(``parity_sample``).  ``--dump-outputs DIR`` writes the scores of the last timed step as
+``DIR/scores.npy`` (float64; the inputs are seeded, so two builds can be compared score for
+score).
 """
 from __future__ import annotations
 
@@ -103,14 +111,22 @@ def parse():
     ap.add_argument("--records", action="store_true",
                     help="q100xdata500: feed the targets as 64-byte CAPI sequence_t records "
                          "(2-bit codes, aligner_Header.h) instead of one code byte per base")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take runs of their own: "
+                         "the host-buffer API rate (pcie_inclusive), the CPU baseline "
+                         "(cpu_baseline) and the oracle re-check of the scores (parity_sample)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the scores of the last timed step to DIR/scores.npy (float64, "
+                         "queries x targets; at N>1 rank 0 writes DIR/scores_rank<r>.npy per "
+                         "rank); past 64 MB in all, a fixed seeded sample of each array")
     ap.add_argument("--cpu-seconds", type=float, default=8.0,
-                    help="wall budget of the CPU-baseline sample (0 disables)")
+                    help="--full: wall budget of the CPU-baseline sample (0 disables)")
     ap.add_argument("--profile-only", action="store_true",
                     help="run warmup+steps and exit without the CPU leg (for rocprofv3)")
     ap.add_argument("--full-parity", action="store_true",
-                    help="re-check EVERY score of rank 0's batch against the oracle (by default "
-                         "batches past 2e10 cells check a sample); reads150x1k: 3.1e11 cells, "
-                         "about 30 s on 16 host cores")
+                    help="--full: re-check EVERY score of rank 0's batch against the oracle (by "
+                         "default batches past 2e10 cells check a sample); reads150x1k: 3.1e11 "
+                         "cells, about 30 s on 16 host cores")
     ap.add_argument("--emulate-ingest", type=float, default=0.0, metavar="MB",
                     help="(rehearsal, N=1) each step also copies MB of device memory on a second "
                          "stream beside the kernel: rank 0's share of the score gather at N>1 "
@@ -369,7 +385,8 @@ def main():
 
     wl = Workload(args, rank, dev, S, torch)
     probe_host = {}
-    if os.environ.get("SWBENCH_PROBE_HOST") == "1":  # (tuning aid) host-API medians by phase
+    # (tuning aid, --full) host-API medians by phase
+    if args.full and os.environ.get("SWBENCH_PROBE_HOST") == "1":
         def _hmed(tag):
             o = np.empty(wl.n, np.int32)
             wl.bank.score_batch(wl.res, wl.offs, wl.lens, out=o)
@@ -441,6 +458,9 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=gdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sg)
 
     cells_rank = wl.cells
     value = world * cells_rank * args.steps / elapsed / 1e9
@@ -528,17 +548,19 @@ def main():
         "cpu_baseline": None,
     }
 
+    # --full: the legs that take runs of their own (a plain run stops at the headline)
     last = sg.last()
     gather = sg.gathered
     if probe_host:
         _hmed("before_host_api_rate")
         out["probe_host"] = probe_host
-    if rank == 0 and world == 1 and wl.d_rec is None and len(wl.queries) == 1:
+    full0 = args.full and rank == 0
+    if full0 and world == 1 and wl.d_rec is None and len(wl.queries) == 1:
         out["pcie_inclusive"] = host_api_rate(wl, last)
-    if rank == 0 and world == 1 and args.cpu_seconds > 0 and wl.kind == "q100xdata500":
+    if full0 and world == 1 and args.cpu_seconds > 0 and wl.kind == "q100xdata500":
         out["cpu_baseline"], out["parity_sample"] = cpu_baseline(
             wl.queries[0], wl.res.reshape(wl.n, wl.L), last[0], wl.L, args.cpu_seconds)
-    elif rank == 0:
+    elif full0:
         out["parity_sample"] = parity_sample(wl, [g for g in gather] if gather else [last],
                                              full_cells=float("inf") if args.full_parity
                                              else 2e10)
@@ -548,6 +570,27 @@ def main():
     wl.bank.close()
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_MAX_BYTES = 64_000_000  # all files of one dump, their .npy headers included
+
+
+def dump_outputs(path, sg):
+    """Rank 0: what the timed path handed its caller in the last timed step, as float64 .npy
+    files under `path`: the score array (queries x targets), and at N>1 every rank's gathered
+    one.  When they would pass DUMP_MAX_BYTES in all, each file holds the values at a fixed
+    seeded set of flat indices (ascending) instead."""
+    os.makedirs(path, exist_ok=True)
+    gather = sg.gathered
+    arrays = ({f"scores_rank{r}": g for r, g in enumerate(gather)} if gather
+              else {"scores": sg.last()})
+    cap = (DUMP_MAX_BYTES // len(arrays) - 256) // 8  # float64 values per file
+    for name, t in arrays.items():
+        a = t.cpu().numpy().astype(np.float64)
+        if a.size > cap:
+            pick = np.unique(np.random.default_rng(20240607).integers(0, a.size, cap))
+            a = a.reshape(-1)[pick]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def host_api_rate(wl, d_sc, iters=15):

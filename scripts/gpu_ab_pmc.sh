@@ -6,10 +6,11 @@ set -u
 cd ${GRAFT_REPO_ROOT:-$(dirname "$0")/..}
 R=$PWD; L=$R/smith-waterman-fpga-module_amd/lib
 mkdir -p gpurun_out
+T=$(mktemp -d); trap 'rm -rf "$T"' EXIT  # (each bench line is read once, then dropped)
 for i in $(seq 1 ${ROUNDS:-3}); do
 for lib in ${AB_LIBS}; do
-SWBANK_LIB=$L/$lib timeout -k 10 300 python bench.py --cpu-seconds 0 --workload ${W:-protein512x1k} > gpurun_out/ab.json 2> gpurun_out/ab.err || { tail -5 gpurun_out/ab.err; exit 3; }
-python -c "import json; d=json.load(open('gpurun_out/ab.json')); print('$lib', d['value'], d['kernel_ms'], d.get('parity_sample'))"
+SWBANK_LIB=$L/$lib timeout -k 10 300 python bench.py --full --cpu-seconds 0 --workload ${W:-protein512x1k} > $T/ab.json 2> $T/ab.err || { tail -5 $T/ab.err; exit 3; }
+python -c "import json; d=json.load(open('$T/ab.json')); print('$lib', d['value'], d['kernel_ms'], d.get('parity_sample'))"
 done; done
 [ "${PMC:-1}" = 1 ] || exit 0
 for lib in ${AB_LIBS}; do

@@ -10,7 +10,7 @@ for shape in ragged uniform; do
   rc=$?; [ $rc -eq 0 ] || { echo "host_ab $shape rc=$rc"; tail -3 "$OUT/host_same_$shape.err"; exit $rc; }
   tail -2 "$OUT/host_same_$shape.json"
   w=ragged; [ $shape = uniform ] && w=q100xdata500
-  timeout -k 10 300 python bench.py --workload $w --cpu-seconds 0 > "$OUT/host_same_bench_$shape.json" 2> "$OUT/host_same_bench_$shape.err"
+  timeout -k 10 300 python bench.py --full --workload $w --cpu-seconds 0 > "$OUT/host_same_bench_$shape.json" 2> "$OUT/host_same_bench_$shape.err"
   rc=$?; [ $rc -eq 0 ] || { echo "bench $w rc=$rc"; tail -3 "$OUT/host_same_bench_$shape.err"; exit $rc; }
   python -c "import json,sys; d=json.load(open(sys.argv[1])); print('bench', sys.argv[2], d['pcie_inclusive'])" "$OUT/host_same_bench_$shape.json" $shape
 done

@@ -13,7 +13,7 @@ if [ -n "$TESTS" ]; then
   rc=$?; echo "pytest rc=$rc"; tail -3 "$OUT/pytest_$TAG.log"; if fatal $rc; then exit $rc; fi
 fi
 for w in ${WORKLOADS:-q100xdata500}; do
-  timeout -k 10 600 python bench.py --workload $w --cpu-seconds 0 ${BENCH_ARGS:-} > "$OUT/bench_${TAG}_$w.json" 2> "$OUT/bench_${TAG}_$w.err"
+  timeout -k 10 600 python bench.py --full --workload $w --cpu-seconds 0 ${BENCH_ARGS:-} > "$OUT/bench_${TAG}_$w.json" 2> "$OUT/bench_${TAG}_$w.err"
   rc=$?; if [ $rc -ne 0 ]; then echo "bench $w rc=$rc"; tail -5 "$OUT/bench_${TAG}_$w.err"; exit $rc; fi
   python - "$OUT/bench_${TAG}_$w.json" <<'PY'
 import json, sys

@@ -3,7 +3,7 @@ import os, sys, time, json, subprocess
 REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 def run(args, env=None):
     e = dict(os.environ, **(env or {}))
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--workload", "ragged", "--cpu-seconds", "0"] + args, capture_output=True, text=True, env=e, timeout=250)
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--workload", "ragged", "--cpu-seconds", "0"] + args, capture_output=True, text=True, env=e, timeout=250)
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     p = d["pcie_inclusive"]
     return [p["ms"], p["ms_best"], p["ms_iqr"]]

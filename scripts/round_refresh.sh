@@ -23,11 +23,11 @@ fi
 if [[ " $PHASES " == *" bench "* ]]; then
 for w in q100xdata500 reads150x1k protein512x1k ragged data500; do
   extra=""; [ $w = reads150x1k ] && extra="--full-parity"  # every pair re-checked (~30 s)
-  timeout -k 10 600 python bench.py --workload $w $extra > "$OUT/bench_${TAG}_$w.json" 2> "$OUT/bench_${TAG}_$w.err"
+  timeout -k 10 600 python bench.py --full --workload $w $extra > "$OUT/bench_${TAG}_$w.json" 2> "$OUT/bench_${TAG}_$w.err"
   rc=$?; step "bench $w" $rc; cut -c1-200 "$OUT/bench_${TAG}_$w.json"; if [ $rc -ne 0 ]; then exit $rc; fi
 done
 # configs[4]'s whole 100k-target batch on one GPU (8-wave blocks, 4 waves per SIMD)
-timeout -k 10 600 python bench.py --workload protein512x1k --ptargets 100000 > "$OUT/bench_${TAG}_protein100k.json" 2> "$OUT/bench_${TAG}_protein100k.err"
+timeout -k 10 600 python bench.py --full --workload protein512x1k --ptargets 100000 > "$OUT/bench_${TAG}_protein100k.json" 2> "$OUT/bench_${TAG}_protein100k.err"
 rc=$?; step "bench protein100k" $rc; cut -c1-200 "$OUT/bench_${TAG}_protein100k.json"; if [ $rc -ne 0 ]; then exit $rc; fi
 fi
 [[ " $PHASES " == *" prof "* ]] || exit 0

@@ -80,31 +80,29 @@ def test_records_match_capi_sequence_t():
 REF_LIB = os.path.join(REPO, "oracle", "_ref", "libaligner_ref.so")
 
 
-@pytest.mark.skipif(not os.path.exists(REF_LIB), reason="oracle/_ref not built")
 def test_pack_2bit_matches_reference_charto2bit():
-    """The reference's own charTo2bit (aligner_Header.c:14-47), compiled into oracle/_ref/."""
-    import ctypes
-    ref = ctypes.CDLL(REF_LIB)
-    ref.charTo2bit.argtypes = [ctypes.c_char_p, ctypes.c_void_p]
-    libc = ctypes.CDLL(None)
-    libc.fflush.argtypes = [ctypes.c_void_p]
-    rng = np.random.default_rng(1)
-    for n in (1, 3, 4, 31, 32, 128, 232):
-        seq = "".join(rng.choice(list("ACGTacgtN"), n))
-        buf = np.zeros(64, np.uint8)
-        # the reference prints a debug trace per base (_DEBUGGING_); run it in a child
-        # process-free way by muting stdout at the fd level
-        fd = os.dup(1)
-        with open(os.devnull, "w") as dn:
-            os.dup2(dn.fileno(), 1)
-            try:
-                ref.charTo2bit(seq.encode(), buf.ctypes.data)
-                libc.fflush(None)
-            finally:
-                os.dup2(fd, 1)
-                os.close(fd)
+    """The reference's own charTo2bit (aligner_Header.c:14-47) on seeded sequences of lengths
+    1, 3, 4, 31, 32, 128 and 232, as recorded in tests/golden/charto2bit_random.tsv
+    (tests/golden/make_charto2bit.py); where oracle/_ref/ is built, the record itself is
+    re-checked against the compiled function."""
+    rows = [l.rstrip("\n").split("\t")
+            for l in open(os.path.join(O.GOLDEN, "charto2bit_random.tsv"))][1:]
+    assert [len(seq) for seq, _ in rows] == [1, 3, 4, 31, 32, 128, 232]
+    ref = None
+    if os.path.exists(REF_LIB):
+        import importlib.util
+        spec = importlib.util.spec_from_file_location(
+            "make_charto2bit", os.path.join(O.GOLDEN, "make_charto2bit.py"))
+        gen = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(gen)
+        ref = gen.load_reference()
+        assert gen.sequences() == [seq for seq, _ in rows]
+    for seq, hexbytes in rows:
+        want = np.frombuffer(bytes.fromhex(hexbytes), np.uint8)
         ours = S.pack_2bit(seq)
-        assert (buf[:len(ours)] == ours).all(), seq
+        assert len(ours) == len(want) and (want == ours).all(), seq
+        if ref is not None:
+            assert (gen.reference_bytes(ref, seq) == want).all(), seq
 
 
 def test_fill_matrix_matches_oracle():

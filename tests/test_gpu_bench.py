@@ -44,7 +44,7 @@ def test_bench_two_ranks_gathered_parity(workload, steps, extra):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", str(steps), "--warmup", "1",
-           "--reps", "64", "--cpu-seconds", "0", "--workload", workload]
+           "--reps", "64", "--full", "--cpu-seconds", "0", "--workload", workload]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=REPO)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json_line(r.stdout)
@@ -62,7 +62,7 @@ def test_bench_gpus_flag_starts_the_ranks():
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(SWBENCH_BACKEND="gloo", SWBENCH_SHARE_GPU="1")
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2",
-           "--warmup", "1", "--reps", "64", "--cpu-seconds", "0"]
+           "--warmup", "1", "--reps", "64", "--full", "--cpu-seconds", "0"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=REPO)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json_line(r.stdout)
@@ -74,6 +74,38 @@ def test_bench_gpus_flag_starts_the_ranks():
     assert ps["ranks"] == 2 and ps["mismatches"] == 0, ps
 
 
+def test_bench_plain_run_is_lean_and_dumps_its_scores(tmp_path):
+    """A plain run (no --full) prints the headline fields and none of the legs that take runs of
+    their own; --dump-outputs writes the last timed step's scores, which are the oracle's on
+    the batch its fixed seed gives (so every run writes the same file)."""
+    import numpy as np
+
+    import bench
+    from oracle import oracle as O
+
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3",
+           "--warmup", "1", "--reps", "3", "--dump-outputs", str(tmp_path / "out")]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=REPO)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = _json_line(r.stdout)
+    assert d["metric"] == "GCUPS" and d["unit"] == "GCUPS" and d["higher_is_better"] is True
+    assert d["steps"] == 3 and d["value"] > 0 and d["ms_per_step"] > 0 and d["dtype"]
+    n, L = 3 * 499, 128
+    q = bench.load_query()
+    cells = len(q) * n * L  # value = cells per step / ms_per_step (both rounded in the line)
+    assert abs(d["value"] - cells / d["ms_per_step"] / 1e6) <= 0.02 * d["value"] + 0.01
+    for leg in ("pcie_inclusive", "parity_sample", "probe_host"):
+        assert leg not in d, leg
+    assert d["cpu_baseline"] is None
+    assert os.listdir(tmp_path / "out") == ["scores.npy"]
+    got = np.load(tmp_path / "out" / "scores.npy")
+    assert got.dtype == np.float64 and got.shape == (1, n)
+    want = O.score_batch(q, bench.make_codes(1000, n, L).reshape(-1),
+                         np.arange(n, dtype=np.uint64) * L, np.full(n, L, np.uint32),
+                         O.dna_matrix(5, -4), -12, -4, O.GAP_MERGED)
+    assert np.array_equal(got[0], want.astype(np.float64))
+
+
 @pytest.mark.parametrize("workload", ["ragged", "data500", "reads150x1k", "protein512x1k"])
 def test_bench_workloads_one_gpu(workload):
     """Every bench workload the driver does not run itself, at reduced size: configs[3] (the
@@ -81,7 +113,7 @@ def test_bench_workloads_one_gpu(workload):
     tail: 4,300 targets = 2,150 pairs, 102 past two pairs per SIMD)."""
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "2", "--warmup", "1",
            "--reps", "64", "--reads", "8192", "--slice", "4", "--ptargets", "4300",
-           "--cpu-seconds", "0", "--workload", workload]
+           "--full", "--cpu-seconds", "0", "--workload", workload]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=REPO)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json_line(r.stdout)
