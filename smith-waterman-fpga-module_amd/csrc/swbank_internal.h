@@ -62,6 +62,14 @@ typedef struct SwkWaveSplit {
   unsigned* wbal_state;
 } SwkWaveSplit;
 
+/* Whether U units of B 32-step blocks may run as balanced ranges on wbal_grid = grid blocks of W
+ * waves: every range holds at least 4 blocks, U B >= 4 W grid (a unit may be cut more than
+ * once).  The one rule of the host's choice (launch()) and of swk_launch_wave's guard. */
+static inline int swk_wbal_admissible(unsigned long long U, unsigned long long B, unsigned W,
+                                      unsigned grid) {
+  return (W == 4 || W == 8) && grid != 0 && U * B >= 4ull * W * grid;
+}
+
 /* Kinds of a launch's fault marks (cross-workgroup hand-off waits that ran out).  Each kind has
  * its own word in the call's group of SWK_FAULT_WORDS words (word ctz(bit) holds bit), so a call
  * whose launches run out in two kinds keeps both (a plain store per kind, no read-modify-write

@@ -1348,8 +1348,11 @@ __global__ void __launch_bounds__(64 * W, W == 8 ? 4 : 1) score_wave_half(const 
   // U / G is -- the ScoreBank's answer to an uneven batch end is the first free module
   // (ScoreBank_v2.v:142-148,164-165); here no slot idles while another runs one unit more.  The
   // cut unit at the range end is scored first (the head, lane state out), the cut unit at the
-  // range start last (the tail, after the predecessor's flag).  U >= G (host): a range holds at
-  // least one unit, so a unit is cut at most once and every wait points to an earlier wave.
+  // range start last (the tail, after the predecessor's flag).  U B >= 4 G (swk_wbal_admissible,
+  // checked by the host's choice and by swk_launch_wave): a range holds at least 4 blocks.  With
+  // U >= G (the host's own choice) a range is at least a unit long and a unit is cut at most
+  // once; below (SWBANK_WAVE_W=8) a unit is cut up to B / 4 times, a range inside one unit being
+  // a middle visit (state in, state out).  Every wait points to an earlier wave.
   // Without: one unit per wave.  One call site of wave_two_pairs for every visit (an inlined
   // copy per visit kind spills).
   const uint32_t G = gridDim.x * W,
@@ -1533,9 +1536,10 @@ extern "C" hipError_t swk_launch_wave(int K, int col0, int prof, int gotoh, int 
     // balanced ranges of the two-pairs kernel (ScoreArgs.wbal_*): no split or tail
     if (!half || K != 8 || edge_in || edge_out || accum || split->pairs || !split->wbal_grid ||
         !split->wbal_flag || !split->wbal_state || !split->fault || split->poll_limit == 0 ||
-        (split->wbal_waves != 4 && split->wbal_waves != 8) || pairs > 0xFFFFFFFFull ||
+        pairs > 0xFFFFFFFFull ||
         // every range at least 4 blocks: U B >= 4 G (a unit may be cut more than once)
-        (pairs + 1) / 2 * split->wbal_blocks < 4ull * split->wbal_waves * split->wbal_grid)
+        !swk_wbal_admissible((pairs + 1) / 2, split->wbal_blocks, split->wbal_waves,
+                             split->wbal_grid))
       return hipErrorInvalidValue;
     a.wbal_blocks = split->wbal_blocks;
     a.wbal_grid = split->wbal_grid;

@@ -178,6 +178,8 @@ sw_status launch(sw_bank* b, const uint8_t* d_res, const uint64_t* d_offs,
     //   at 3 waves per SIMD (12,500 targets: -11 %), so 4-wave blocks stay.
     // * 4-wave blocks (3 waves per SIMD, 3,072 slots) with at least one unit per slot and a
     //   remainder.
+    // * either way every range holds at least 4 blocks (swk_wbal_admissible: short targets need
+    //   more than a unit per slot); else the unbalanced launch with its split or segmented tail.
     // SWBANK_WAVE_BAL=0 disables; SWBANK_WAVE_W=4 / =8 forces the block size (=8 down to ranges
     // of 4 blocks: tests of the chained visits).
     bool wbal = false;
@@ -185,16 +187,21 @@ sw_status launch(sw_bank* b, const uint8_t* d_res, const uint64_t* d_offs,
         sforce < 0 && pairs <= 0xFFFFFFFFull && env_int("SWBANK_WAVE_BAL", 1) != 0) {
       const size_t U = (pairs + 1) / 2, B = (max_len + 31 + 31) / 32;
       const int wforce = env_int("SWBANK_WAVE_W", 0);
+      // W = 8 first, then W = 4, else no balanced launch: both under swk_wbal_admissible (every
+      // range at least 4 blocks), the rule swk_launch_wave checks again
       int W = wforce == 4 ? 4 : 8;
       unsigned grid = swk_wave_half_grid(gotoh ? 1 : 0, (b->pad + 1) * b->wPS16, W);
-      if (W == 8 && !(grid && (wforce == 8 ? U * B >= 4 * (size_t)W * grid
-                                            : U >= (size_t)W * grid))) {
+      bool ok = W == 8 && swk_wbal_admissible(U, B, 8, grid) &&
+                (wforce == 8 || U >= (size_t)8 * grid);
+      if (!ok) {
         W = 4;
         grid = swk_wave_half_grid(gotoh ? 1 : 0, (b->pad + 1) * b->wPS16, W);
+        const size_t G4 = (size_t)4 * grid;
+        ok = swk_wbal_admissible(U, B, 4, grid) && U >= G4 && U % G4;
       }
       const size_t G = (size_t)W * grid;
-      uint32_t* fw = grid ? fault_word(b) : nullptr;
-      if (grid && fw && (W == 8 || (U >= G && U % G))) {
+      uint32_t* fw = ok ? fault_word(b) : nullptr;
+      if (ok && fw) {
         const size_t sw = (G + 1) * 36 * 64;  // (WBAL_WORDS per lane)
         HIPOK(b, b->wbal_state.reserve(sw));
         if (b->wbal_flag.cap < G + 1) {  // zeroed once: flags carry wbal_gen
