@@ -61,8 +61,11 @@ extern "C" {
  *        multi-device device calls copy each device's share into its own HBM.
  * ABI 6: sw_counters.wave_balanced_timeouts; sw_score_batch_device_multi (each device scores
  *        a batch already resident in its own HBM, only the int32 scores cross xGMI); every entry
- *        point leaves the caller's current HIP device as it found it. */
+ *        point leaves the caller's current HIP device as it found it.
+ * ABI 6 additions (purely additive, the version stays 6; test SWBANK_HAS_ALIGN): alignments of
+ *        chosen hits -- sw_alignment, sw_align_hits, sw_align_hits_device, sw_cigar_string. */
 #define SWBANK_ABI_VERSION 6
+#define SWBANK_HAS_ALIGN 1
 
 typedef int32_t sw_status;
 enum {
@@ -254,6 +257,86 @@ sw_status sw_best_hit(sw_bank *bank, const int32_t *scores, const uint64_t *ids,
 sw_status sw_best_hit_device(sw_bank *bank, const int32_t *d_scores, const uint64_t *d_ids,
                              size_t n, uint64_t *d_out, void *stream);
 
+/* ---- alignments of chosen hits (ABI 6 addition) -------------------------------------------
+ * The score calls return a number per pair; these return, for a caller-chosen list of hits
+ * (typically the best few dozen to few thousand of a batch), where the alignment lies and the
+ * alignment itself -- what ssearch36 prints per hit in the reference's data/alignments500.txt
+ * ("Smith-Waterman score: 78; 66.7% identity ... in 51 nt overlap (9-55:62-110)").
+ *
+ * Semantics, the same for both gap models, every entry point and every device layout:
+ *   score   what sw_score_batch returns for the pair (int32 arithmetic: no 16-bit bound).
+ *   end     among the cells whose value is `score`: the smallest t_end, then the smallest q_end
+ *           (so no other maximal cell lies in [0..q_end] x [0..t_end], which makes a reverse
+ *           local pass over the reversed prefixes find the start).
+ *   start   among the starts of optimal alignments ending there: the largest t_start, then the
+ *           largest q_start (the same rule on the reversed problem).
+ *   CIGAR   an optimal path from (q_start, t_start) to (q_end, t_end); an op is len << 4 | code,
+ *           adjacent equal codes merged, the first and the last op are M; it consumes
+ *           q_end - q_start + 1 query codes and t_end - t_start + 1 target codes, and re-scoring
+ *           it under the bank's model gives `score`: a gap run of k columns costs
+ *           open + k * extend, a run being a maximal stretch of one code under SW_GAP_GOTOH and a
+ *           maximal stretch of I and D ops together under SW_GAP_MERGED (the merged gap matrix
+ *           lets a gap turn the corner without re-opening).  Among co-optimal paths, walking
+ *           back from the end cell: the diagonal (M) first, then a gap from the left (D), then a
+ *           gap from above (I); a gap run opens rather than extends when both are optimal.
+ *   empty   a pair scoring 0 (a zero-length target included): SW_ALIGN_EMPTY, every coordinate
+ *           0, no ops.
+ * A record with SW_ALIGN_NO_PATH has exact coordinates, no ops, and n_columns = n_identities = 0.
+ *
+ * Status: SW_ERR_STATE without penalties or a query, or while a query set of more than one
+ * query is loaded; SW_ERR_UNSUPPORTED for SW_GAP_MERGED penalties whose largest substitution
+ * score exceeds open + extend (the only case in which the HDL's first-column rule,
+ * SW_ProcessingElement_v1.0.v:131-141, changes a score: the reversed pass cannot apply it); a
+ * latched hand-off fault of an earlier device call is returned as by the other device calls.
+ * Inputs are byte codes only (no records, no packed codes). */
+enum { SW_CIGAR_M = 0, SW_CIGAR_I = 1, SW_CIGAR_D = 2 };  /* BAM codes: I consumes query only,
+                                                             D consumes target only          */
+enum { SW_ALIGN_EMPTY = 1,    /* score 0: no alignment, all coordinates 0, no CIGAR          */
+       SW_ALIGN_NO_PATH = 2 };/* coordinates valid, CIGAR not produced (window over budget
+                                 or the caller's CIGAR space too small)                      */
+typedef struct sw_alignment {
+  uint64_t index;             /* position of the target in the batch (the hit list's entry)  */
+  uint64_t id;                /* ids[index], or index                                        */
+  int32_t  score;
+  uint32_t flags;
+  uint32_t q_start, q_end, t_start, t_end;   /* 0-based, inclusive                           */
+  uint32_t n_columns, n_identities;          /* alignment columns; columns with equal codes  */
+  uint32_t cigar_offset, cigar_len;          /* ops at cigar[cigar_offset .. +cigar_len)     */
+} sw_alignment;
+
+/* Device buffers, asynchronous on `stream` (NULL = the bank's stream): aligns targets
+ * d_hits[0..n_hits) (uint64 batch positions < n, any order, repeats allowed) of the batch
+ * (d_residues, d_offsets, d_lens, d_ids as for sw_score_batch_device; max_len >= every
+ * d_lens[k]) against the loaded query and writes d_out[h] for hit h.  Hit h's ops go to
+ * d_cigar + h * cigar_stride (cigar_offset = h * cigar_stride); a path of more than cigar_stride
+ * ops gets SW_ALIGN_NO_PATH.  d_cigar == NULL or cigar_stride == 0: coordinates only, every
+ * non-empty hit gets SW_ALIGN_NO_PATH.  The path needs one direction byte per cell of the
+ * window [q_start..q_end] x [t_start..t_end]; that memory is bounded by
+ * SWBANK_ALIGN_MB (MiB, default 256) and the hits run in chunks that fit, sized here from
+ * max_len x the query length so that nothing is read back; if one such window does not fit,
+ * every non-empty hit gets SW_ALIGN_NO_PATH.  On a multi-device bank the buffers and the stream
+ * belong to the root device (devices[0]) and the work runs there: hit lists are small.
+ * sw_last_kernel reports e.g. "align i32 hits=2 chunks=1"; with sw_bank_set_timing the end /
+ * start passes and the path passes are bracketed as one launch each. */
+sw_status sw_align_hits_device(sw_bank *bank, const uint8_t *d_residues,
+                               const uint64_t *d_offsets, const uint32_t *d_lens,
+                               const uint64_t *d_ids, size_t n, uint32_t max_len,
+                               const uint64_t *d_hits, size_t n_hits, sw_alignment *d_out,
+                               uint32_t *d_cigar, uint32_t cigar_stride, void *stream);
+
+/* Host buffers, blocking; the batch as for sw_score_batch (a target outside the residues, a
+ * code outside the alphabet in a listed target, or a hit >= n is SW_ERR_ARG).  Only the listed
+ * targets are gathered and uploaded.  The chunks are sized from the hits' actual windows (one
+ * small copy of the coordinates back), so only a single window over SWBANK_ALIGN_MB gets
+ * SW_ALIGN_NO_PATH.  The CIGARs are packed back to back in hit order into cigar[0..cigar_cap),
+ * *cigar_used (may be NULL) = ops written; a hit whose ops no longer fit gets SW_ALIGN_NO_PATH
+ * (later, shorter ones may still fit) and the call still returns SW_OK.  cigar == NULL or
+ * cigar_cap == 0: coordinates only. */
+sw_status sw_align_hits(sw_bank *bank, const uint8_t *residues, size_t residues_len,
+                        const uint64_t *offsets, const uint32_t *lens, const uint64_t *ids,
+                        size_t n, const uint64_t *hits, size_t n_hits, sw_alignment *out,
+                        uint32_t *cigar, size_t cigar_cap, size_t *cigar_used);
+
 /* ---- profiling (≙ the CAPI AFU's cycle counters, capi_sample_aligner/hdl-verliog/afu.v
  *      _DEBUGGING_ "calculation #N completed, runtime: C cycles") ------------------------- */
 /* When enabled, every launch is bracketed by hipEvents on the stream it runs on. */
@@ -327,6 +410,10 @@ size_t sw_pack_2bit(const char *ascii, size_t n, uint8_t *out);
 size_t sw_unpack_2bit(const uint8_t *packed, size_t n, uint8_t *codes);
 /* Fill a substitution matrix: DNA (alpha 5) from match/mismatch, or BLOSUM62 (alpha 24). */
 sw_status sw_fill_matrix(int32_t alphabet, int32_t match, int32_t mismatch, int8_t *matrix);
+/* CIGAR ops -> text, e.g. "15M2I17M4D13M" (an op code past D prints as '?'): writes at most
+ * cap - 1 characters and a NUL into buf (nothing when cap == 0; buf may then be NULL) and
+ * returns the length the whole string needs, excluding the NUL. */
+size_t sw_cigar_string(const uint32_t *ops, size_t n_ops, char *buf, size_t cap);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,55 @@
+/* swbank_align.h — the launch interface of the alignment kernels (swbank_kalign.hip), shared
+ * with the host unit that drives them (swbank_align.hip).  Internal. */
+#ifndef SWBANK_ALIGN_H
+#define SWBANK_ALIGN_H
+
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+/* One call's arguments: the batch, the hit list (hits == NULL: hit h is target h), the query's
+ * codes and the alpha x alpha matrix on the device, the records and the CIGAR buffer (cigar_stride
+ * 0: coordinates only), per-wave scratch rows (waves x 2 x scols x 8 B; scols >= every length). */
+typedef struct SwkAlign {
+  int gotoh;
+  const uint8_t* res;
+  const uint64_t* offs;
+  const uint32_t* lens;
+  const uint64_t* ids;
+  const uint64_t* hits;
+  size_t n_hits;
+  const uint8_t* query;
+  uint32_t qlen;
+  const int8_t* mat;
+  uint32_t alpha, pad;
+  int32_t padscore;
+  uint32_t O, E;
+  void* out; /* sw_alignment[n_hits] */
+  uint32_t* cigar;
+  uint32_t cigar_stride;
+  void* scratch;
+  uint32_t scols;
+  size_t waves; /* a multiple of 4 */
+} SwkAlign;
+
+/* Where one hit's window sits in the direction store (dwords) and its ops in the CIGAR buffer. */
+typedef struct SwkAlignPlan {
+  uint64_t dir_off, dir_cap, cig_off;
+  uint32_t cig_cap, reserved;
+} SwkAlignPlan;
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+/* Dwords of direction store a window of rows x cols cells takes:
+ * ceil(rows / 256) strips x (cols + 63) steps x 64 lanes. */
+uint64_t swk_align_dir_dwords(uint32_t rows, uint32_t cols);
+hipError_t swk_launch_align_ends(const SwkAlign* p, hipStream_t st);
+hipError_t swk_launch_align_paths(const SwkAlign* p, const uint32_t* list, size_t h0, size_t count,
+                                  const SwkAlignPlan* plan, uint64_t slot, uint32_t* dirs,
+                                  hipStream_t st);
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* SWBANK_ALIGN_H */

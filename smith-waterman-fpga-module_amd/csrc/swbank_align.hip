@@ -1,0 +1,335 @@
+// swbank_align.hip — alignments of chosen hits (include/swbank.h "alignments of chosen hits",
+// DESIGN.md §3.9): the two ABI entries, the chunking of the direction store, the host call's
+// staging.  The kernels are in swbank_kalign.hip.
+#include "swbank_bank.h"
+
+namespace {
+
+// Direction-store budget in dwords (SWBANK_ALIGN_MB, MiB, default 256).
+uint64_t dir_budget() {
+  return ((uint64_t)std::max(1, env_int("SWBANK_ALIGN_MB", 256)) << 20) / 4;
+}
+
+// The query's codes and the matrix on the device, built on first use per (penalties, query)
+// and uploaded on the bank stream like the other query tables (prepare_i32).
+sw_status prepare_align(sw_bank* b) {
+  if (b->al_ready) return SW_OK;
+  const size_t ql = b->query.size(), ml = b->matrix.size();
+  HIPOK(b, hipEventSynchronize(b->ev_ready));  // the staging buffer is free again
+  HIPOK(b, b->stage.reserve(ql + ml));
+  HIPOK(b, b->al_tab.reserve(ql + ml));
+  HIPOK(b, hipStreamWaitEvent(b->stream, b->ev_used, 0));
+  if (ql) std::memcpy(b->stage.p, b->query.data(), ql);
+  std::memcpy(b->stage.p + ql, b->matrix.data(), ml);
+  HIPOK(b, hipMemcpyAsync(b->al_tab.p, b->stage.p, ql + ml, hipMemcpyHostToDevice, b->stream));
+  HIPOK(b, hipEventRecord(b->ev_ready, b->stream));
+  b->al_ready = true;
+  return SW_OK;
+}
+
+// The state both entries need; on return the bank is prepare()d.
+sw_status align_ready(sw_bank* b) {
+  if (!b->have_pen || !b->have_query)
+    return fail(b, SW_ERR_STATE, "penalties or query not loaded");
+  if (b->qset.size() > 1)
+    return fail(b, SW_ERR_STATE, "a query set is loaded: alignments take one query");
+  const sw_status st = prepare(b);
+  if (st != SW_OK) return st;
+  if (!b->gotoh() && b->col0)
+    return fail(b, SW_ERR_UNSUPPORTED,
+                "alignments under merged gaps need max substitution score <= open + extend");
+  if ((size_t)b->alpha * b->alpha != b->matrix.size() || b->alpha >= 25 || b->pad >= 25)
+    return fail(b, SW_ERR_UNSUPPORTED, "alignment kernels: alphabet %d too large", b->alpha);
+  return prepare_align(b);
+}
+
+struct Timed {  // one bracketed launch group (sw_bank_set_timing)
+  sw_bank* b;
+  hipStream_t st;
+  sw_bank::Ev ev{};
+  sw_status begin() {
+    if (!b->timing) return SW_OK;
+    HIPOK(b, hipEventCreate(&ev.a));
+    HIPOK(b, hipEventCreate(&ev.c));
+    HIPOK(b, hipEventRecord(ev.a, st));
+    ev.b = ev.a;
+    return SW_OK;
+  }
+  sw_status end() {
+    if (!b->timing) return SW_OK;
+    HIPOK(b, hipEventRecord(ev.c, st));
+    b->events.push_back(ev);
+    return SW_OK;
+  }
+};
+
+// The launch block of a call over `nh` hits of at most `max_len` columns; reserves the scratch.
+sw_status align_block(sw_bank* b, SwkAlign& p, size_t nh, uint32_t max_len) {
+  const uint32_t scols = std::max(max_len, 1u);
+  const size_t budget = (size_t)std::max(1, env_int("SWBANK_EDGE_MB", 2048)) << 20;
+  const size_t waves = swk_i32_waves(nh, scols, budget);
+  HIPOK(b, b->al_scr.reserve(waves * 2 * scols));
+  p.gotoh = b->gotoh() ? 1 : 0;
+  p.n_hits = nh;
+  p.query = b->al_tab.p;
+  p.qlen = (uint32_t)b->query.size();
+  p.mat = reinterpret_cast<const int8_t*>(b->al_tab.p + b->query.size());
+  p.alpha = (uint32_t)b->alpha;
+  p.pad = b->pad;
+  p.padscore = (int32_t)b->S - 255;
+  p.O = b->O;
+  p.E = b->E;
+  p.scratch = b->al_scr.p;
+  p.scols = scols;
+  p.waves = waves;
+  return SW_OK;
+}
+
+// Passes C and D in slots of the largest possible window (the device call: nothing read back).
+sw_status paths_by_slot(sw_bank* b, const SwkAlign& p, uint32_t max_len, hipStream_t hs,
+                        size_t& chunks) {
+  chunks = 0;
+  const uint64_t slot = swk_align_dir_dwords(p.qlen, max_len), budget = dir_budget();
+  if (slot == 0 || slot > budget) return SW_OK;  // every non-empty hit keeps SW_ALIGN_NO_PATH
+  const size_t per = (size_t)std::min<uint64_t>(budget / slot, p.n_hits);
+  HIPOK(b, b->al_dirs.reserve((size_t)(slot * per)));
+  for (size_t h0 = 0; h0 < p.n_hits; h0 += per, ++chunks)
+    HIPOK(b, swk_launch_align_paths(&p, nullptr, h0, std::min(per, p.n_hits - h0), nullptr, slot,
+                                    b->al_dirs.p, hs));
+  return SW_OK;
+}
+
+void name_kernel(sw_bank* b, size_t hits, size_t chunks) {
+  snprintf(b->last_kernel, sizeof(b->last_kernel), "align i32 hits=%zu chunks=%zu", hits, chunks);
+}
+
+sw_status device_call(sw_bank* b, const uint8_t* d_res, const uint64_t* d_offs,
+                      const uint32_t* d_lens, const uint64_t* d_ids, uint32_t max_len,
+                      const uint64_t* d_hits, size_t n_hits, sw_alignment* d_out,
+                      uint32_t* d_cigar, uint32_t stride, hipStream_t hs) {
+  SwkAlign p{};
+  p.res = d_res;
+  p.offs = d_offs;
+  p.lens = d_lens;
+  p.ids = d_ids;
+  p.hits = d_hits;
+  p.out = d_out;
+  p.cigar = d_cigar;
+  p.cigar_stride = d_cigar ? stride : 0;
+  sw_status st = align_block(b, p, n_hits, max_len);
+  if (st != SW_OK) return st;
+  HIPOK(b, hipStreamWaitEvent(hs, b->ev_ready, 0));  // the query's codes are uploaded
+  HIPOK(b, hipStreamWaitEvent(hs, b->ev_used, 0));   // bank scratch is free
+  Timed ab{b, hs};
+  if ((st = ab.begin()) != SW_OK) return st;
+  HIPOK(b, swk_launch_align_ends(&p, hs));
+  if ((st = ab.end()) != SW_OK) return st;
+  size_t chunks = 0;
+  if (p.cigar_stride) {
+    Timed cd{b, hs};
+    if ((st = cd.begin()) != SW_OK) return st;
+    if ((st = paths_by_slot(b, p, max_len, hs, chunks)) != SW_OK) return st;
+    if ((st = cd.end()) != SW_OK) return st;
+  }
+  HIPOK(b, hipEventRecord(b->ev_used, hs));
+  name_kernel(b, n_hits, chunks);
+  return SW_OK;
+}
+
+}  // namespace
+
+extern "C" sw_status sw_align_hits_device(sw_bank* b, const uint8_t* d_res,
+                                          const uint64_t* d_offs, const uint32_t* d_lens,
+                                          const uint64_t* d_ids, size_t n, uint32_t max_len,
+                                          const uint64_t* d_hits, size_t n_hits,
+                                          sw_alignment* d_out, uint32_t* d_cigar,
+                                          uint32_t cigar_stride, void* stream) {
+  DevGuard dev_guard(b);  // on the bank's device; the caller's is restored on return (ABI 6)
+  if (!b) return SW_ERR_ARG;
+  if (b->is_multi()) {  // on the root device, where the caller's buffers are
+    sw_bank* k = b->kids[0];
+    if (!b->have_query) return fail(b, SW_ERR_STATE, "penalties or query not loaded");
+    if (b->qset.size() > 1)
+      return fail(b, SW_ERR_STATE, "a query set is loaded: alignments take one query");
+    const sw_status st = sw_align_hits_device(k, d_res, d_offs, d_lens, d_ids, n, max_len, d_hits,
+                                              n_hits, d_out, d_cigar, cigar_stride,
+                                              stream ? stream : k->stream);
+    if (st != SW_OK) return fail(b, st, "device %d: %s", k->device, k->err);
+    snprintf(b->last_kernel, sizeof(b->last_kernel), "%s", k->last_kernel);
+    return SW_OK;
+  }
+  // a hand-off fault latched by an earlier device call is returned before anything runs
+  if (const sw_status fs = take_fault(b, 0); fs != SW_OK) return fs;
+  sw_status st = align_ready(b);
+  if (st != SW_OK) return st;
+  if (n_hits == 0) return SW_OK;
+  if (!d_res || !d_offs || !d_lens || !d_hits || !d_out || n == 0)
+    return fail(b, SW_ERR_ARG, "null device buffer or an empty batch");
+  if (n_hits > 0xFFFFFFFFull) return fail(b, SW_ERR_ARG, "hit lists hold < 2^32 hits");
+  if (d_cigar && cigar_stride && (uint64_t)n_hits * cigar_stride > 0xFFFFFFFFull)
+    return fail(b, SW_ERR_ARG, "n_hits x cigar_stride must fit 32 bits (cigar_offset)");
+  HIPOK(b, hipSetDevice(b->device));
+  hipStream_t hs = stream ? reinterpret_cast<hipStream_t>(stream) : b->stream;
+  return device_call(b, d_res, d_offs, d_lens, d_ids, max_len, d_hits, n_hits, d_out, d_cigar,
+                     cigar_stride, hs);
+}
+
+extern "C" sw_status sw_align_hits(sw_bank* b, const uint8_t* residues, size_t residues_len,
+                                   const uint64_t* offsets, const uint32_t* lens,
+                                   const uint64_t* ids, size_t n, const uint64_t* hits,
+                                   size_t n_hits, sw_alignment* out, uint32_t* cigar,
+                                   size_t cigar_cap, size_t* cigar_used) {
+  DevGuard dev_guard(b);  // on the bank's device; the caller's is restored on return (ABI 6)
+  if (!b) return SW_ERR_ARG;
+  if (cigar_used) *cigar_used = 0;
+  if (b->is_multi()) {  // on the root device: hit lists are small
+    sw_bank* k = b->kids[0];
+    if (!b->have_query) return fail(b, SW_ERR_STATE, "penalties or query not loaded");
+    if (b->qset.size() > 1)
+      return fail(b, SW_ERR_STATE, "a query set is loaded: alignments take one query");
+    const sw_status st = sw_align_hits(k, residues, residues_len, offsets, lens, ids, n, hits,
+                                       n_hits, out, cigar, cigar_cap, cigar_used);
+    if (st != SW_OK) return fail(b, st, "device %d: %s", k->device, k->err);
+    snprintf(b->last_kernel, sizeof(b->last_kernel), "%s", k->last_kernel);
+    return SW_OK;
+  }
+  sw_status st = align_ready(b);
+  if (st != SW_OK) return st;
+  if (n_hits == 0) return SW_OK;
+  if (!offsets || !lens || !hits || !out) return fail(b, SW_ERR_ARG, "null host buffer");
+  if (n_hits > 0xFFFFFFFFull) return fail(b, SW_ERR_ARG, "hit lists hold < 2^32 hits");
+  // validate and gather the listed targets (a repeated hit is gathered again)
+  std::vector<uint64_t> goffs(n_hits);
+  std::vector<uint32_t> glens(n_hits);
+  uint64_t total = 0;
+  uint32_t max_len = 0;
+  for (size_t h = 0; h < n_hits; ++h) {
+    const uint64_t t = hits[h];
+    if (t >= n) return fail(b, SW_ERR_ARG, "hit %zu: target %llu >= n = %zu", h,
+                            (unsigned long long)t, n);
+    const uint64_t o = offsets[t], l = lens[t];
+    if (l && (!residues || o > residues_len || l > residues_len - o))
+      return fail(b, SW_ERR_ARG, "target %llu outside the residues", (unsigned long long)t);
+    goffs[h] = total;
+    glens[h] = (uint32_t)l;
+    total += l;
+    max_len = std::max(max_len, (uint32_t)l);
+  }
+  std::vector<uint8_t> gres(std::max<uint64_t>(total, 1), 0);
+  for (size_t h = 0; h < n_hits; ++h) {
+    const uint8_t* src = glens[h] ? residues + offsets[hits[h]] : nullptr;
+    for (uint32_t i = 0; i < glens[h]; ++i) {
+      if (src[i] >= (uint32_t)b->alpha)
+        return fail(b, SW_ERR_ARG, "target %llu code %u at %u outside alphabet %d",
+                    (unsigned long long)hits[h], src[i], i, b->alpha);
+      gres[goffs[h] + i] = src[i];
+    }
+  }
+  HIPOK(b, hipSetDevice(b->device));
+  hipStream_t hs = b->stream;
+  HIPOK(b, b->al_res.reserve(gres.size()));
+  HIPOK(b, b->al_offs.reserve(n_hits));
+  HIPOK(b, b->al_lens.reserve(n_hits));
+  HIPOK(b, b->al_out.reserve(n_hits));
+  HIPOK(b, hipStreamWaitEvent(hs, b->ev_ready, 0));
+  HIPOK(b, hipStreamWaitEvent(hs, b->ev_used, 0));  // an earlier call may still read the buffers
+  HIPOK(b, hipMemcpyAsync(b->al_res.p, gres.data(), gres.size(), hipMemcpyHostToDevice, hs));
+  HIPOK(b, hipMemcpyAsync(b->al_offs.p, goffs.data(), n_hits * 8, hipMemcpyHostToDevice, hs));
+  HIPOK(b, hipMemcpyAsync(b->al_lens.p, glens.data(), n_hits * 4, hipMemcpyHostToDevice, hs));
+  __atomic_fetch_add(&b->ctr.h2d_bytes, gres.size() + n_hits * 12, __ATOMIC_RELAXED);
+  SwkAlign p{};
+  p.res = b->al_res.p;
+  p.offs = b->al_offs.p;
+  p.lens = b->al_lens.p;
+  p.out = b->al_out.p;
+  if ((st = align_block(b, p, n_hits, max_len)) != SW_OK) return st;
+  Timed ab{b, hs};
+  if ((st = ab.begin()) != SW_OK) return st;
+  HIPOK(b, swk_launch_align_ends(&p, hs));
+  if ((st = ab.end()) != SW_OK) return st;
+  HIPOK(b, hipMemcpyAsync(out, b->al_out.p, n_hits * sizeof(sw_alignment), hipMemcpyDeviceToHost,
+                          hs));
+  HIPOK(b, hipStreamSynchronize(hs));
+  size_t chunks = 0;
+  std::vector<uint32_t> ops;
+  cigar_cap = std::min<size_t>(cigar_cap, 0xFFFFFFFFu);  // (cigar_offset is 32 bits)
+  if (cigar && cigar_cap) {
+    // the windows that fit the budget, in hit order, in chunks that fit it together; each hit's
+    // ops in a slot of rows + columns of the window (a path never has more ops)
+    const uint64_t budget = dir_budget();
+    std::vector<uint32_t> list;
+    std::vector<SwkAlignPlan> plan;
+    std::vector<size_t> cut{0};  // chunk c = positions [cut[c], cut[c + 1])
+    uint64_t used = 0, cig = 0, most = 0;
+    for (size_t h = 0; h < n_hits; ++h) {
+      const sw_alignment& r = out[h];
+      if (r.score <= 0) continue;
+      const uint32_t Q = r.q_end - r.q_start + 1, L = r.t_end - r.t_start + 1;
+      const uint64_t need = swk_align_dir_dwords(Q, L);
+      if (need > budget) continue;  // SW_ALIGN_NO_PATH, coordinates stay
+      if (used + need > budget) {
+        cut.push_back(list.size());
+        used = 0;
+      }
+      list.push_back((uint32_t)h);
+      plan.push_back(SwkAlignPlan{used, need, cig, Q + L, 0});
+      used += need;
+      most = std::max(most, used);
+      cig += (uint64_t)Q + L;
+    }
+    cut.push_back(list.size());
+    if (!list.empty()) {
+      HIPOK(b, b->al_dirs.reserve((size_t)most));
+      HIPOK(b, b->al_cig.reserve((size_t)cig));
+      HIPOK(b, b->al_list.reserve(list.size()));
+      HIPOK(b, b->al_plan.reserve(plan.size()));
+      HIPOK(b, hipMemcpyAsync(b->al_list.p, list.data(), list.size() * 4, hipMemcpyHostToDevice,
+                              hs));
+      HIPOK(b, hipMemcpyAsync(b->al_plan.p, plan.data(), plan.size() * sizeof(SwkAlignPlan),
+                              hipMemcpyHostToDevice, hs));
+      p.cigar = b->al_cig.p;
+      p.cigar_stride = 1;  // (places come from the plan)
+      Timed cd{b, hs};
+      if ((st = cd.begin()) != SW_OK) return st;
+      for (size_t c = 0; c + 1 < cut.size(); ++c) {
+        if (cut[c + 1] == cut[c]) continue;
+        HIPOK(b, swk_launch_align_paths(&p, b->al_list.p + cut[c], 0, cut[c + 1] - cut[c],
+                                        b->al_plan.p + cut[c], 0, b->al_dirs.p, hs));
+        ++chunks;
+      }
+      if ((st = cd.end()) != SW_OK) return st;
+      ops.resize((size_t)cig);
+      HIPOK(b, hipMemcpyAsync(out, b->al_out.p, n_hits * sizeof(sw_alignment),
+                              hipMemcpyDeviceToHost, hs));
+      HIPOK(b, hipMemcpyAsync(ops.data(), b->al_cig.p, ops.size() * 4, hipMemcpyDeviceToHost, hs));
+      HIPOK(b, hipStreamSynchronize(hs));
+    }
+    // pack the ops back to back in hit order
+    size_t at = 0, k = 0;
+    for (size_t h = 0; h < n_hits; ++h) {
+      sw_alignment& r = out[h];
+      const bool planned = k < list.size() && list[k] == h;
+      const uint64_t from = planned ? plan[k].cig_off : 0;
+      if (planned) ++k;
+      r.cigar_offset = 0;
+      if (r.flags != 0 || !planned) continue;
+      if (r.cigar_len > cigar_cap - at) {
+        r.flags = SW_ALIGN_NO_PATH;
+        r.cigar_len = r.n_columns = r.n_identities = 0;
+        continue;
+      }
+      std::memcpy(cigar + at, ops.data() + from, (size_t)r.cigar_len * 4);
+      r.cigar_offset = (uint32_t)at;
+      at += r.cigar_len;
+    }
+    if (cigar_used) *cigar_used = at;
+  }
+  HIPOK(b, hipEventRecord(b->ev_used, hs));
+  for (size_t h = 0; h < n_hits; ++h) {  // the records speak of the caller's batch
+    out[h].index = hits[h];
+    out[h].id = ids ? ids[hits[h]] : hits[h];
+    if (!(cigar && cigar_cap)) out[h].cigar_offset = 0;
+  }
+  name_kernel(b, n_hits, chunks);
+  return SW_OK;
+}

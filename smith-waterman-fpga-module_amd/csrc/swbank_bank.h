@@ -3,7 +3,8 @@
 // Units: swbank_bank.hip (lifecycle, penalties, queries, the query tables), swbank_launch.hip
 // (kernel choice and launches, the device-buffer API), swbank_feeder.hip (the chunked
 // host-buffer feeder and the host API), swbank_stream.hip (streamed host batches, one kernel
-// per call), swbank_multi.hip (multi-device banks and the RCCL gather).
+// per call), swbank_multi.hip (multi-device banks and the RCCL gather), swbank_align.hip
+// (alignments of chosen hits).
 #ifndef SWBANK_BANK_H
 #define SWBANK_BANK_H
 
@@ -34,6 +35,7 @@
 #endif
 
 #include "swbank.h"
+#include "swbank_align.h"
 #include "swbank_internal.h"
 #include "swbank_pack.h"
 
@@ -402,6 +404,17 @@ struct sw_bank {
   uint32_t i32_strips = 0;
   DevBuf<uint2> i32prof, i32scr;
   DevBuf<unsigned long long> best_key;  // sw_best_hit_device scratch
+  // alignments of chosen hits (swbank_align.hip): the query's codes and the matrix on the
+  // device (al_tab: codes, then alpha x alpha scores; built on first use per query), per-wave
+  // scratch rows, the direction store; the host-buffer call's gathered targets, records, ops,
+  // window plan and chunk lists
+  bool al_ready = false;
+  DevBuf<uint8_t> al_tab, al_res;
+  DevBuf<uint2> al_scr;
+  DevBuf<uint32_t> al_dirs, al_lens, al_cig, al_list;
+  DevBuf<uint64_t> al_offs;
+  DevBuf<sw_alignment> al_out;
+  DevBuf<SwkAlignPlan> al_plan;
   struct Seg { int W; size_t off, off16; };  // rows = W*R (last may be shorter); word offsets
                                               // in qtab and qtab16
   std::vector<Seg> segs;

@@ -198,6 +198,16 @@ extern "C" void sw_bank_destroy(sw_bank* b) {
   b->best_dev.release();
   b->i32prof.release();
   b->i32scr.release();
+  b->al_tab.release();
+  b->al_res.release();
+  b->al_scr.release();
+  b->al_dirs.release();
+  b->al_lens.release();
+  b->al_cig.release();
+  b->al_list.release();
+  b->al_offs.release();
+  b->al_out.release();
+  b->al_plan.release();
   b->dperm.release();
   b->dsort.release();
   b->bal_state.release();
@@ -825,6 +835,7 @@ sw_status prepare(sw_bank* b) {
   b->smax = smax;
   b->col0 = col0;
   b->i32_ready = false;
+  b->al_ready = false;
   b->mq_ready = false;
   b->dirty = false;
   return SW_OK;

@@ -8,7 +8,7 @@
  *     271-285), one per library record, in library order (the RTL printed completion order).
  *
  * Usage: swbank -q query.fa -l library.fa [-p match,mismatch,open,extend] [-P] [-g]
- *               [-d device[,device...]] [-o out.txt] [-T] [-R scores.txt] [-b]
+ *               [-d device[,device...]] [-o out.txt] [-T] [-R scores.txt] [-b] [-A k]
  *   -p  penalties (default 5,-4,-12,-4: ScoreBank_v1_tb.sv:16-19, data/smith-waterman.py:6-10)
  *   -P  protein mode (BLOSUM62; -p gives only open,extend)      -g  Gotoh gap model
  *   -T  testbench transcript format "@     0ns: %10s score: \t%d"
@@ -17,6 +17,12 @@
  *   -d  HIP device, or a comma list for a multi-device bank (the library is dealt over the
  *       devices, length-balanced, and the scores gathered back with RCCL; ScoreBank_v2.v:76-148
  *       spreads targets over MODULES the same way)
+ *   -A  after the score lines, the alignments of the k best library records (score descending,
+ *       ties in library order, chosen on the host from the scores; sw_align_hits), each as
+ *       ssearch36 reports a hit (data/alignments500.txt): ">>name (len nt)", " s-w opt: S", the
+ *       summary line "Smith-Waterman score: S; P% identity (P% similar) in N nt overlap
+ *       (qs-qe:ts-te)" with 1-based coordinates ("aa" with -P), then "cigar: ..." (a record
+ *       scoring 0 prints the first two lines only)
  *   -b  also print the bank's best hit ("best: >name score: S", ≙ max / vld_max) to stderr
  * FASTA: '>' starts a record (name = first token); sequence lines are concatenated; CR/LF,
  * blank lines and lower case are accepted; bytes outside the alphabet encode to N (DNA) or X
@@ -104,15 +110,77 @@ fail:
 static void usage(const char *argv0) {
   fprintf(stderr,
           "usage: %s -q query.fa -l library.fa [-p match,mismatch,open,extend] [-P] [-g]\n"
-          "          [-d device[,device...]] [-o out.txt] [-T] [-R scores.txt] [-b]\n",
+          "          [-d device[,device...]] [-o out.txt] [-T] [-R scores.txt] [-b] [-A k]\n",
           argv0);
+}
+
+/* The k best records (score descending, ties in library order), aligned and printed. */
+static const int32_t *g_sort_scores;
+static int by_score(const void *a, const void *b) {
+  const uint64_t x = *(const uint64_t *)a, y = *(const uint64_t *)b;
+  if (g_sort_scores[x] != g_sort_scores[y]) return g_sort_scores[x] > g_sort_scores[y] ? -1 : 1;
+  return x < y ? -1 : x > y;
+}
+
+static int print_alignments(FILE *out, sw_bank *bank, const uint8_t *res, size_t total,
+                            const uint64_t *offs, const uint32_t *lens, const int32_t *scores,
+                            const fasta_t *lib, size_t k, const char *unit) {
+  uint64_t *order = malloc(lib->n * sizeof(uint64_t));
+  sw_alignment *al = malloc(k * sizeof(sw_alignment));
+  size_t cap = k, used = 0;
+  if (!order || !al) {
+    free(order);
+    free(al);
+    return 3;
+  }
+  for (size_t i = 0; i < lib->n; ++i) order[i] = i;
+  g_sort_scores = scores;
+  qsort(order, lib->n, sizeof(uint64_t), by_score);
+  for (size_t i = 0; i < k; ++i) cap += 2 * (size_t)lens[order[i]]; /* ops a path can have */
+  uint32_t *cig = malloc(cap * sizeof(uint32_t));
+  sw_status st = cig ? sw_align_hits(bank, res, total, offs, lens, NULL, lib->n, order, k, al, cig,
+                                     cap, &used)
+                     : SW_ERR_NOMEM;
+  if (st != SW_OK) {
+    fprintf(stderr, "swbank: %s: %s\n", sw_status_string(st), sw_last_error(bank));
+  } else {
+    for (size_t i = 0; i < k; ++i) {
+      const sw_alignment *a = &al[i];
+      fprintf(out, ">>%s (%u %s)\n s-w opt: %d\n", lib->names[a->index], lens[a->index], unit,
+              a->score);
+      if (a->flags & SW_ALIGN_EMPTY) continue;
+      if (a->flags == 0) {
+        const double pct = 100.0 * a->n_identities / a->n_columns;
+        fprintf(out,
+                "Smith-Waterman score: %d; %.1f%% identity (%.1f%% similar) in %u %s overlap "
+                "(%u-%u:%u-%u)\n",
+                a->score, pct, pct, a->n_columns, unit, a->q_start + 1, a->q_end + 1,
+                a->t_start + 1, a->t_end + 1);
+        const size_t need = sw_cigar_string(cig + a->cigar_offset, a->cigar_len, NULL, 0);
+        char *text = malloc(need + 1);
+        if (text) {
+          sw_cigar_string(cig + a->cigar_offset, a->cigar_len, text, need + 1);
+          fprintf(out, "cigar: %s\n", text);
+          free(text);
+        }
+      } else { /* coordinates without a path (a window past SWBANK_ALIGN_MB) */
+        fprintf(out, "Smith-Waterman score: %d; no path (%u-%u:%u-%u)\ncigar: *\n", a->score,
+                a->q_start + 1, a->q_end + 1, a->t_start + 1, a->t_end + 1);
+      }
+    }
+  }
+  free(order);
+  free(al);
+  free(cig);
+  return st == SW_OK ? 0 : 3;
 }
 
 int main(int argc, char **argv) {
   const char *qpath = NULL, *lpath = NULL, *opath = NULL, *pen = NULL, *rpath = NULL;
   int protein = 0, gotoh = 0, device = -1, transcript = 0, best = 0, opt;
   int ndev = 0, devs[SW_MAX_DEVICES];
-  while ((opt = getopt(argc, argv, "q:l:p:Pgd:o:TR:bh")) != -1) {
+  long nalign = 0;
+  while ((opt = getopt(argc, argv, "q:l:p:Pgd:o:TR:bA:h")) != -1) {
     switch (opt) {
       case 'q': qpath = optarg; break;
       case 'l': lpath = optarg; break;
@@ -133,6 +201,12 @@ int main(int argc, char **argv) {
         break;
       }
       case 'b': best = 1; break;
+      case 'A': {
+        char *end;
+        nalign = strtol(optarg, &end, 10);
+        if (end == optarg || *end || nalign < 0) return usage(argv[0]), 1;
+        break;
+      }
       case 'o': opath = optarg; break;
       case 'T': transcript = 1; break;
       case 'R': rpath = optarg; break;
@@ -225,6 +299,16 @@ int main(int argc, char **argv) {
       fprintf(out, "@%6dns: %10s score: \t%10d\n", 0, nm, scores[k]);
     else
       fprintf(out, "%s score: %d\n", nm, scores[k]);
+  }
+  if (nalign > 0 && lib.n) {
+    int rc = print_alignments(out, bank, res, total, offs, lens, scores, &lib,
+                              (size_t)nalign < lib.n ? (size_t)nalign : lib.n,
+                              protein ? "aa" : "nt");
+    if (rc) {
+      if (opath) fclose(out);
+      sw_bank_destroy(bank);
+      return rc;
+    }
   }
   if (opath) fclose(out);
   uint64_t bid = 0;

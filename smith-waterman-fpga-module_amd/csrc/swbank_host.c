@@ -6,6 +6,7 @@
  *   charTo2bit     capi_sample_aligner/software-C,C++/include/aligner_Header.c:14-47
  *                  (2 bits per base, LSB first, 4 bases per byte; 'N' and other bytes -> 00b)
  */
+#include <stdio.h>
 #include <string.h>
 
 #include "swbank.h"
@@ -126,4 +127,19 @@ sw_status sw_fill_matrix(int32_t alphabet, int32_t match, int32_t mismatch, int8
     for (int b = 0; b < SW_DNA_ALPHA; ++b)
       m[a * SW_DNA_ALPHA + b] = (int8_t)((a == b && a < 4) ? match : mismatch);
   return SW_OK;
+}
+
+size_t sw_cigar_string(const uint32_t *ops, size_t n_ops, char *buf, size_t cap) {
+  size_t need = 0;
+  for (size_t k = 0; ops && k < n_ops; ++k) {
+    char tmp[16];
+    const uint32_t code = ops[k] & 15u;
+    const int w = snprintf(tmp, sizeof(tmp), "%u%c", (unsigned)(ops[k] >> 4),
+                           code == SW_CIGAR_M ? 'M' : code == SW_CIGAR_I ? 'I'
+                           : code == SW_CIGAR_D ? 'D' : '?');
+    for (int c = 0; c < w; ++c, ++need)
+      if (buf && need + 1 < cap) buf[need] = tmp[c];
+  }
+  if (buf && cap) buf[need < cap ? need : cap - 1] = 0;
+  return need;
 }

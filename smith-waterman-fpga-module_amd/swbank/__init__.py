@@ -16,6 +16,7 @@ construction raises.
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 import os
 from typing import Iterable, Optional, Sequence, Tuple
 
@@ -44,6 +45,7 @@ EXPORTS = (
     "sw_best_hit_device", "sw_batch_best", "sw_bank_devices", "sw_load_queries",
     "sw_query_count", "sw_score_batch_device_range", "sw_bank_counters",
     "sw_bank_counters_ex", "sw_bank_sync", "sw_score_batch_device_multi",
+    "sw_align_hits", "sw_align_hits_device", "sw_cigar_string",
 )
 ABI_VERSION = 6
 COUNTERS = ("stream_calls", "stream_reruns", "stream_declined", "chunked_calls", "device_sorts",
@@ -51,6 +53,8 @@ COUNTERS = ("stream_calls", "stream_reruns", "stream_declined", "chunked_calls",
             "balanced_timeouts", "tail_timeouts", "handoff_reruns", "wave_balanced_timeouts",
             "h2d_bytes")
 MAX_DEVICES = 16
+CIGAR_M, CIGAR_I, CIGAR_D = 0, 1, 2          # BAM codes: I consumes query only, D target only
+ALIGN_EMPTY, ALIGN_NO_PATH = 1, 2            # sw_alignment.flags
 RECORD_BYTES, RECORD_MAX_BASES = 64, 232
 
 
@@ -66,6 +70,69 @@ class DeviceBatch(ctypes.Structure):
                 ("d_lens", ctypes.c_void_p), ("n", ctypes.c_size_t),
                 ("min_len", ctypes.c_uint32), ("max_len", ctypes.c_uint32),
                 ("d_scores", ctypes.c_void_p), ("stream", ctypes.c_void_p)]
+
+
+class AlignmentRecord(ctypes.Structure):
+    """sw_alignment: one hit's record as the C ABI writes it (56 bytes)."""
+    _fields_ = [("index", ctypes.c_uint64), ("id", ctypes.c_uint64), ("score", ctypes.c_int32),
+                ("flags", ctypes.c_uint32), ("q_start", ctypes.c_uint32),
+                ("q_end", ctypes.c_uint32), ("t_start", ctypes.c_uint32),
+                ("t_end", ctypes.c_uint32), ("n_columns", ctypes.c_uint32),
+                ("n_identities", ctypes.c_uint32), ("cigar_offset", ctypes.c_uint32),
+                ("cigar_len", ctypes.c_uint32)]
+
+
+ALIGNMENT_DTYPE = np.dtype([(n, np.dtype(t)) for n, t in AlignmentRecord._fields_])
+
+
+@dataclasses.dataclass
+class Alignment:
+    """One aligned hit (sw_alignment with its ops): coordinates 0-based and inclusive; `ops`
+    the CIGAR as len << 4 | code, `cigar` its text (empty without a path)."""
+    index: int
+    id: int
+    score: int
+    flags: int
+    q_start: int
+    q_end: int
+    t_start: int
+    t_end: int
+    n_columns: int
+    n_identities: int
+    ops: Tuple[int, ...] = ()
+    cigar: str = ""
+
+    @property
+    def empty(self) -> bool:
+        return bool(self.flags & ALIGN_EMPTY)
+
+    @property
+    def has_path(self) -> bool:
+        return self.flags == 0
+
+
+def cigar_string(ops) -> str:
+    """CIGAR ops (len << 4 | code) -> text, e.g. "15M2I17M4D13M" (sw_cigar_string)."""
+    a = np.ascontiguousarray(ops, dtype=np.uint32).reshape(-1)
+    need = lib().sw_cigar_string(_p(a) if a.size else None, a.size, None, 0)
+    buf = ctypes.create_string_buffer(need + 1)
+    lib().sw_cigar_string(_p(a) if a.size else None, a.size, buf, need + 1)
+    return buf.value.decode()
+
+
+def alignments_from(records: np.ndarray, cigar: np.ndarray) -> list:
+    """Alignment objects from an ALIGNMENT_DTYPE array and the op buffer its offsets index."""
+    out = []
+    for r in records:
+        ops = ()
+        if r["flags"] == 0:
+            ops = tuple(int(x) for x in cigar[int(r["cigar_offset"]):
+                                              int(r["cigar_offset"]) + int(r["cigar_len"])])
+        out.append(Alignment(int(r["index"]), int(r["id"]), int(r["score"]), int(r["flags"]),
+                             int(r["q_start"]), int(r["q_end"]), int(r["t_start"]),
+                             int(r["t_end"]), int(r["n_columns"]), int(r["n_identities"]), ops,
+                             cigar_string(ops) if ops else ""))
+    return out
 
 
 class _Config(ctypes.Structure):
@@ -134,6 +201,9 @@ def lib() -> ctypes.CDLL:
         "sw_load_queries": (i32, [P, sz, P, P, P, P]),
         "sw_query_count": (sz, [P]),
         "sw_score_batch_device_multi": (i32, [P, P, sz, P, P]),
+        "sw_align_hits": (i32, [P, P, sz, P, P, P, sz, P, sz, P, P, sz, P]),
+        "sw_align_hits_device": (i32, [P, P, P, P, P, sz, u32, P, sz, P, P, u32, P]),
+        "sw_cigar_string": (sz, [P, sz, P, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -402,6 +472,40 @@ class ScoreBank:
                                  bt.get("d_scores", 0) or None, bt.get("stream", 0) or None)
         self._check(lib().sw_score_batch_device_multi(self._h, arr, len(batches),
                                                       d_gathered or None, stream or None))
+
+    # alignments of chosen hits
+    def align_hits(self, residues: np.ndarray, offsets: np.ndarray, lens: np.ndarray, hits,
+                   ids: Optional[np.ndarray] = None, cigar_cap: Optional[int] = None) -> list:
+        """sw_align_hits: Alignment objects for targets hits[0..) (batch positions, any order,
+        repeats allowed) of the host batch.  cigar_cap: ops the call may return in all (default:
+        enough for every path; 0: coordinates only, every non-empty hit ALIGN_NO_PATH)."""
+        res, offs, ln, idv = validate_batch(residues, offsets, lens, ids)
+        hv = np.ascontiguousarray(hits, dtype=np.uint64).reshape(-1)
+        out = np.zeros(max(len(hv), 1), dtype=ALIGNMENT_DTYPE)
+        if cigar_cap is None:  # runs alternate with M runs: at most 2 x columns + 1 ops a path
+            sel = hv[hv < len(ln)].astype(np.int64)
+            cigar_cap = 2 * int(ln[sel].astype(np.int64).sum()) + len(hv)
+        cig = np.zeros(max(cigar_cap, 1), dtype=np.uint32)
+        used = ctypes.c_size_t()
+        self._check(lib().sw_align_hits(self._h, _p(res), res.size, _p(offs), _p(ln),
+                                        _p(idv) if idv is not None else None, len(ln), _p(hv),
+                                        len(hv), _p(out), _p(cig) if cigar_cap else None,
+                                        cigar_cap, ctypes.byref(used)))
+        return alignments_from(out[:len(hv)], cig)
+
+    def align_targets(self, seqs: Iterable[np.ndarray], hits) -> list:
+        return self.align_hits(*pack_targets(list(seqs)), hits)
+
+    def align_hits_device(self, d_res: int, d_offs: int, d_lens: int, n: int, max_len: int,
+                          d_hits: int, n_hits: int, d_out: int, d_cigar: int = 0,
+                          cigar_stride: int = 0, stream: int = 0, d_ids: int = 0):
+        """sw_align_hits_device: device pointers (ints); d_out receives n_hits sw_alignment
+        records (ALIGNMENT_DTYPE, 56 bytes each), hit h's ops go to d_cigar + h * cigar_stride.
+        Async on `stream` (0: the bank's own stream; sync() before reading)."""
+        self._check(lib().sw_align_hits_device(self._h, d_res or None, d_offs or None,
+                                               d_lens or None, d_ids or None, n, max_len,
+                                               d_hits or None, n_hits, d_out or None,
+                                               d_cigar or None, cigar_stride, stream or None))
 
     def counters(self) -> dict:
         """sw_bank_counters: feeder / fallback counts since the bank was created."""
