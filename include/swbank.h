@@ -126,6 +126,13 @@ void sw_bank_destroy(sw_bank *bank);
 const char *sw_last_error(const sw_bank *bank);
 
 /* ---- ld_penalties / LUT ---------------------------------------------------------------- */
+/* matrix[q * alpha + t] scores query code q against target code t; it need not be symmetric.
+ * Accepted: 0 >= gap_open, gap_extend >= -32767 (else SW_ERR_ARG) and any int8 entries.  Two
+ * combinations are refused with SW_ERR_RANGE by the first scoring or alignment call (with
+ * S = max(0, largest entry), smin = smallest entry, o = -gap_open, e = -gap_extend):
+ *   S - smin > 254          (the 8-bit biased tables)
+ *   Gotoh and o + e + S > 65535   (the 16-bit columns; the merged model has no such limit)
+ * Everything else is scored exactly (tests/test_gpu_params.py). */
 sw_status sw_set_penalties(sw_bank *bank, int32_t match, int32_t mismatch, int32_t gap_open,
                            int32_t gap_extend);
 sw_status sw_set_matrix(sw_bank *bank, const int8_t *matrix, int32_t alpha, int32_t gap_open,
