@@ -11,6 +11,8 @@ import swbank as S
 from oracle import oracle as O
 
 import align_check as AC
+from align_cases import QLENS, boundary_case as _boundary_case, device_align as _device_align, \
+    protein_case
 
 pytestmark = pytest.mark.gpu
 
@@ -36,33 +38,6 @@ def _dna_bank(model, pen, **kw):
     bank = S.ScoreBank(gap_model=model, **kw)
     bank.set_penalties(*pen)
     return bank
-
-
-def _device_align(bank, seqs, hits, stride, ids=None):
-    """sw_align_hits_device on torch buffers -> Alignment objects."""
-    import torch
-    res, offs, lens = S.pack_targets(seqs)
-    dev = torch.device("cuda", 0)
-    hv = np.asarray(hits, np.uint64)
-    d_res = torch.from_numpy(res).to(dev)
-    d_offs = torch.from_numpy(offs.view(np.int64)).to(dev)
-    d_lens = torch.from_numpy(lens.view(np.int32)).to(dev)
-    d_hits = torch.from_numpy(hv.view(np.int64)).to(dev)
-    d_ids = torch.from_numpy(np.asarray(ids, np.uint64).view(np.int64)).to(dev) \
-        if ids is not None else None
-    d_out = torch.full((len(hv) * S.ALIGNMENT_DTYPE.itemsize,), 0x3C, dtype=torch.uint8, device=dev)
-    d_cig = torch.full((max(1, len(hv) * stride),), 0x3C3C3C3C, dtype=torch.int32, device=dev)
-    torch.cuda.synchronize()
-    bank.align_hits_device(d_res.data_ptr(), d_offs.data_ptr(), d_lens.data_ptr(), len(seqs),
-                           max(int(lens.max()), 1), d_hits.data_ptr(), len(hv), d_out.data_ptr(),
-                           d_cig.data_ptr() if stride else 0, stride,
-                           d_ids=d_ids.data_ptr() if d_ids is not None else 0)
-    bank.sync()
-    rec = d_out.cpu().numpy().view(S.ALIGNMENT_DTYPE)
-    cig = d_cig.cpu().numpy().view(np.uint32)
-    if stride:
-        assert [int(r["cigar_offset"]) for r in rec] == [h * stride for h in range(len(hv))]
-    return S.alignments_from(rec, cig)
 
 
 def _check_all(q, seqs, hits, alns, sub, go, ge, model, brute, want_path=True):
@@ -108,46 +83,7 @@ def test_golden_hits(model):
     _check_all(q, seqs, hits, alns, sub, -12, -4, model, brute)
 
 
-# ---- 2. boundaries: lane, chunk and strip edges ----------------------------------------------
-QLENS = [1, 3, 4, 5, 63, 64, 65, 255, 256, 257, 300, 513]
-TLENS = [0, 1, 63, 64, 65, 127, 128, 129, 200]
-
-
-def _planted(rng, q, L, alpha=4):
-    """A slice of q with substitutions and 1-5-base insertions and deletions, in random flanks,
-    L codes in all."""
-    if L == 0:
-        return np.zeros(0, np.uint8)
-    n = min(len(q), L)
-    a = int(rng.integers(0, len(q) - n + 1))
-    core = [int(c) for c in q[a:a + n]]
-    for _ in range(max(1, n // 12)):
-        core[int(rng.integers(0, len(core)))] = int(rng.integers(0, alpha))
-    for _ in range(int(rng.integers(1, 4))):
-        k, pos = int(rng.integers(1, 6)), int(rng.integers(0, len(core) + 1))
-        if rng.random() < 0.5:
-            core[pos:pos] = [int(c) for c in rng.integers(0, alpha, k)]
-        elif len(core) > k:
-            del core[pos:pos + k]
-    core = core[:L]
-    flank = L - len(core)
-    left = int(rng.integers(0, flank + 1))
-    return np.concatenate([rng.integers(0, alpha, left), np.array(core, np.int64),
-                           rng.integers(0, alpha, flank - left)]).astype(np.uint8)
-
-
-def _boundary_case(qlen, seed):
-    rng = np.random.default_rng(seed)
-    q = rng.integers(0, 4, qlen).astype(np.uint8)
-    lens = [int(x) for x in rng.choice(TLENS, 24)]
-    lens[:len(TLENS)] = TLENS  # every length occurs
-    seqs = [rng.integers(0, 4, L).astype(np.uint8) if k % 2 == 0 else _planted(rng, q, L)
-            for k, L in enumerate(lens)]
-    hits = [int(x) for x in rng.permutation(24)]
-    hits += [hits[3], hits[17]]  # two repeats
-    return q, seqs, hits
-
-
+# ---- 2. boundaries: lane, chunk and strip edges (the inputs: tests/align_cases.py) ---------
 @pytest.mark.parametrize("model", MODELS)
 @pytest.mark.parametrize("pen", [REF, ALT])
 @pytest.mark.parametrize("qlen", QLENS)
@@ -166,12 +102,7 @@ def test_boundaries_dna(qlen, pen, model):
 
 # ---- 3. protein ---------------------------------------------------------------------------------
 def test_protein_gotoh():
-    rng = np.random.default_rng(33)
-    q = rng.integers(0, 20, 300).astype(np.uint8)
-    lens = [400, 1, 37, 256, 257, 399, 128, 300] * 2
-    seqs = [rng.integers(0, 20, L).astype(np.uint8) if k % 2 == 0 else _planted(rng, q, L, 20)
-            for k, L in enumerate(lens)]
-    hits = list(range(16))
+    q, seqs, hits = protein_case()
     brute = _cached("protein",
                     lambda: AC.brute_ends_batch(O, q, seqs, O.BLOSUM62, -11, -1, S.GAP_GOTOH))
     with S.ScoreBank(alphabet=S.ALPHABET_PROTEIN, gap_model=S.GAP_GOTOH) as bank:
