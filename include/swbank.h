@@ -25,6 +25,9 @@
  *         INPUT order (the RTL reports completion order; callers re-keyed by ID).
  *   sw_best_hit
  *       ≙ the bank's max / vld_max outputs (ScoreBank_v2.v:42-43, declared but never driven).
+ *   sw_top_hits / sw_top_hits_device
+ *       ≙ the "The best scores are:" list ssearch36 prints over the bank's scores (the
+ *         reference's data/alignments500.txt): the k best, highest score first.
  *   sw_encode_ascii
  *       ≙ ConvertToBase (ScoreBank_v1_tb.sv:44-52): A=2 G=3 T=0 C=1 (lower case too);
  *         any other byte -> SW_DNA_N (4), which mismatches every code.
@@ -63,9 +66,12 @@ extern "C" {
  *        a batch already resident in its own HBM, only the int32 scores cross xGMI); every entry
  *        point leaves the caller's current HIP device as it found it.
  * ABI 6 additions (purely additive, the version stays 6; test SWBANK_HAS_ALIGN): alignments of
- *        chosen hits -- sw_alignment, sw_align_hits, sw_align_hits_device, sw_cigar_string. */
+ *        chosen hits -- sw_alignment, sw_align_hits, sw_align_hits_device, sw_cigar_string;
+ *        (test SWBANK_HAS_TOPK) the k best hits of a score matrix -- sw_top_hits,
+ *        sw_top_hits_device. */
 #define SWBANK_ABI_VERSION 6
 #define SWBANK_HAS_ALIGN 1
+#define SWBANK_HAS_TOPK 1
 
 typedef int32_t sw_status;
 enum {
@@ -263,6 +269,57 @@ sw_status sw_best_hit(sw_bank *bank, const int32_t *scores, const uint64_t *ids,
  * n <= 2^32. */
 sw_status sw_best_hit_device(sw_bank *bank, const int32_t *d_scores, const uint64_t *d_ids,
                              size_t n, uint64_t *d_out, void *stream);
+
+/* ---- the k best hits of a score matrix (ABI 6 addition) -------------------------------------
+ * What connects the score calls to the alignment calls on the device: the list ssearch36 prints
+ * as "The best scores are:" (the reference's data/alignments500.txt), the best hits of a query,
+ * highest score first.  sw_score_batch_device, sw_top_hits_device and sw_align_hits_device run
+ * back to back on one stream with no host round trip: d_hits is the align call's hit list.
+ *
+ * Semantics, the same for both entry points and every device layout:
+ *   order     row i selects from scores[i*n .. i*n+n) the targets with score >= min_score
+ *             (INT32_MIN: no threshold), ordered by score descending, then batch position
+ *             ascending -- sw_batch_best's "lowest index with the maximum score", continued.
+ *             The first c_i = min(k, n, number of qualifying targets) of them go to
+ *             hits[i*k + j], j < c_i, as batch positions in [0, n).  This is exactly the first
+ *             c_i entries of a stable descending sort of the row; the result is bitwise identical
+ *             from run to run, however many targets share the k-th score.
+ *   optional  hit_scores, hit_ids and counts may each be NULL.  hit_scores[i*k + j] is the hit's
+ *             score, hit_ids[i*k + j] is ids ? ids[position] : position (ids holds n entries, shared
+ *             by the rows), counts[i] is c_i.
+ *   the rest  slots j >= c_i of every array given are written with SW_HIT_NONE / INT32_MIN /
+ *             SW_HIT_NONE, so the caller's buffers are fully defined after the call.  A caller
+ *             who passes no threshold and k <= n knows c_i = k without reading anything back and
+ *             may pass d_hits and k straight to sw_align_hits_device.
+ *   input     any int32 is a legal score, negative values, INT32_MIN and INT32_MAX included.
+ * SW_ERR_ARG (nothing is written): a NULL bank, scores or hits; n, nq or k == 0;
+ * k > SW_TOP_MAX_K; n > 2^32 (as sw_best_hit_device); nq * n or nq * k overflowing size_t. */
+#define SW_TOP_MAX_K 4096              /* one query's selection is ordered in one workgroup's LDS:
+                                          4096 64-bit keys = 32 KiB */
+#define SW_HIT_NONE UINT64_MAX         /* a slot past the row's count */
+
+/* Device buffers, asynchronous on `stream` (NULL = the bank's).
+ * d_scores holds nq rows of n int32 scores, query-major, as sw_score_batch_device
+ * writes them for a query set.  nq is given by the caller; the bank's loaded
+ * query or query set is not consulted, so penalties and query need not be loaded.
+ * A latched hand-off fault of an earlier device call is returned as by the other device calls.
+ * On a multi-device bank the buffers and the stream belong to the root device (devices[0]) and
+ * the work runs there, as for sw_best_hit_device.  The bank owns the scratch and orders a call
+ * after the previous call's use of it, so calls on different streams need no synchronisation
+ * between them; sw_bank_sync waits for the last one.  sw_last_kernel reports
+ * "top k=<k> nq=<nq> n=<n>"; with sw_bank_set_timing the whole selection is bracketed as one
+ * launch. */
+sw_status sw_top_hits_device(sw_bank *bank, const int32_t *d_scores, const uint64_t *d_ids,
+                             size_t n, size_t nq, size_t k, int32_t min_score,
+                             uint64_t *d_hits, int32_t *d_hit_scores, uint64_t *d_hit_ids,
+                             uint32_t *d_counts, void *stream);
+
+/* Host buffers, blocking: uploads the scores, runs the same kernels, copies the result back.
+ * hit_ids are looked up on the host, so ids are not uploaded.  Not counted in
+ * sw_counters.h2d_bytes. */
+sw_status sw_top_hits(sw_bank *bank, const int32_t *scores, const uint64_t *ids,
+                      size_t n, size_t nq, size_t k, int32_t min_score,
+                      uint64_t *hits, int32_t *hit_scores, uint64_t *hit_ids, uint32_t *counts);
 
 /* ---- alignments of chosen hits (ABI 6 addition) -------------------------------------------
  * The score calls return a number per pair; these return, for a caller-chosen list of hits

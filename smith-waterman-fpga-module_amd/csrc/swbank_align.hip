@@ -43,26 +43,6 @@ sw_status align_ready(sw_bank* b) {
   return prepare_align(b);
 }
 
-struct Timed {  // one bracketed launch group (sw_bank_set_timing)
-  sw_bank* b;
-  hipStream_t st;
-  sw_bank::Ev ev{};
-  sw_status begin() {
-    if (!b->timing) return SW_OK;
-    HIPOK(b, hipEventCreate(&ev.a));
-    HIPOK(b, hipEventCreate(&ev.c));
-    HIPOK(b, hipEventRecord(ev.a, st));
-    ev.b = ev.a;
-    return SW_OK;
-  }
-  sw_status end() {
-    if (!b->timing) return SW_OK;
-    HIPOK(b, hipEventRecord(ev.c, st));
-    b->events.push_back(ev);
-    return SW_OK;
-  }
-};
-
 // The launch block of a call over `nh` hits of at most `max_len` columns; reserves the scratch.
 sw_status align_block(sw_bank* b, SwkAlign& p, size_t nh, uint32_t max_len) {
   const uint32_t scols = std::max(max_len, 1u);

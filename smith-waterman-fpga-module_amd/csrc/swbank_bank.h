@@ -4,7 +4,7 @@
 // (kernel choice and launches, the device-buffer API), swbank_feeder.hip (the chunked
 // host-buffer feeder and the host API), swbank_stream.hip (streamed host batches, one kernel
 // per call), swbank_multi.hip (multi-device banks and the RCCL gather), swbank_align.hip
-// (alignments of chosen hits).
+// (alignments of chosen hits), swbank_top.hip (the k best hits of a score matrix).
 #ifndef SWBANK_BANK_H
 #define SWBANK_BANK_H
 
@@ -97,6 +97,12 @@ extern "C" hipError_t swk_launch_i32(int gotoh, const uint8_t* res, const uint64
                                      const void* prof, uint32_t nstrips, uint32_t qlen,
                                      uint32_t pad, uint32_t O, uint32_t E, int32_t* scores,
                                      void* scratch, uint32_t scols, size_t waves, hipStream_t st);
+
+extern "C" size_t swk_top_state_words(void);
+extern "C" hipError_t swk_top_hits(const int32_t* scores, const uint64_t* ids, size_t n, size_t nq,
+                                   size_t k, int32_t min_score, unsigned long long* state,
+                                   unsigned long long* keys, uint64_t* hits, int32_t* hit_scores,
+                                   uint64_t* hit_ids, uint32_t* counts, hipStream_t st);
 
 // ---- helpers shared by the units ----------------------------------------------------
 inline int env_int(const char* name, int dflt) {
@@ -415,6 +421,14 @@ struct sw_bank {
   DevBuf<uint64_t> al_offs;
   DevBuf<sw_alignment> al_out;
   DevBuf<SwkAlignPlan> al_plan;
+  // the k best hits (swbank_top.hip): the select's per-row state and key slots; the host call's
+  // scores and results on the device; ev_top follows the last call's use of the four, on
+  // whichever stream it ran, and the next call's stream waits for it
+  DevBuf<unsigned long long> top_state, top_keys;
+  DevBuf<int32_t> top_scores, top_hsc;
+  DevBuf<uint64_t> top_hits;
+  DevBuf<uint32_t> top_cnt;
+  hipEvent_t ev_top = nullptr;
   struct Seg { int W; size_t off, off16; };  // rows = W*R (last may be shorter); word offsets
                                               // in qtab and qtab16
   std::vector<Seg> segs;
@@ -595,6 +609,32 @@ sw_status fail(sw_bank* b, sw_status st, const char* fmt, ...);
       return fail((bank), SW_ERR_HIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_),    \
                   __FILE__, __LINE__);                                                    \
   } while (0)
+
+struct Timed {  // one bracketed launch group (sw_bank_set_timing)
+  sw_bank* b;
+  hipStream_t st;
+  sw_bank::Ev ev{};
+  sw_status begin() {
+    if (!b->timing) return SW_OK;
+    HIPOK(b, hipEventCreate(&ev.a));
+    HIPOK(b, hipEventCreate(&ev.c));
+    HIPOK(b, hipEventRecord(ev.a, st));
+    ev.b = ev.a;
+    return SW_OK;
+  }
+  sw_status end() {
+    if (!b->timing) return SW_OK;
+    HIPOK(b, hipEventRecord(ev.c, st));
+    b->events.push_back(ev);
+    return SW_OK;
+  }
+  void drop() {  // a group that failed after begin(): its events are not kept
+    if (!b->timing) return;
+    if (ev.a) (void)hipEventDestroy(ev.a);
+    if (ev.c) (void)hipEventDestroy(ev.c);
+    ev = {};
+  }
+};
 
 // RCCL for the multi-device score gather (SURVEY §8 e), loaded on first use (swbank_multi.hip).
 struct Rccl {

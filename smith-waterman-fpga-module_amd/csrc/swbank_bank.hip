@@ -176,6 +176,7 @@ extern "C" void sw_bank_destroy(sw_bank* b) {
   }
   (void)hipSetDevice(b->device);
   if (b->stream) (void)hipStreamSynchronize(b->stream);
+  if (b->ev_top) (void)hipEventSynchronize(b->ev_top);  // the last top-hits call, on any stream
   uint64_t nl;
   double pm, sm;
   (void)sw_bank_timing(b, &nl, &pm, &sm);
@@ -190,6 +191,7 @@ extern "C" void sw_bank_destroy(sw_bank* b) {
   if (b->ev_ready) (void)hipEventDestroy(b->ev_ready);
   if (b->ev_used) (void)hipEventDestroy(b->ev_used);
   if (b->best_ev) (void)hipEventDestroy(b->best_ev);
+  if (b->ev_top) (void)hipEventDestroy(b->ev_top);
   if (b->ev_join) (void)hipEventDestroy(b->ev_join);
   for (hipEvent_t e : b->deal_ev) (void)hipEventDestroy(e);
   b->fb_idx.release();
@@ -208,6 +210,12 @@ extern "C" void sw_bank_destroy(sw_bank* b) {
   b->al_offs.release();
   b->al_out.release();
   b->al_plan.release();
+  b->top_state.release();
+  b->top_keys.release();
+  b->top_scores.release();
+  b->top_hsc.release();
+  b->top_hits.release();
+  b->top_cnt.release();
   b->dperm.release();
   b->dsort.release();
   b->bal_state.release();
@@ -344,6 +352,7 @@ extern "C" sw_status sw_bank_sync(sw_bank* b) {
   hipError_t e = hipSetDevice(b->device);
   // ev_used follows every launch of a scoring call on the stream it ran on
   if (e == hipSuccess && b->ev_used) e = hipEventSynchronize(b->ev_used);
+  if (e == hipSuccess && b->ev_top) e = hipEventSynchronize(b->ev_top);  // ... of a top-hits call
   if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
   (void)hipSetDevice(cur);
   HIPOK(b, e);

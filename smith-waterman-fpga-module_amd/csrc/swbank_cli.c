@@ -114,7 +114,8 @@ static void usage(const char *argv0) {
           argv0);
 }
 
-/* The k best records (score descending, ties in library order), aligned and printed. */
+/* The k best records (score descending, ties in library order), aligned and printed: picked on
+ * the device by sw_top_hits, or, for k past SW_TOP_MAX_K, by a sort of the whole library here. */
 static const int32_t *g_sort_scores;
 static int by_score(const void *a, const void *b) {
   const uint64_t x = *(const uint64_t *)a, y = *(const uint64_t *)b;
@@ -124,8 +125,10 @@ static int by_score(const void *a, const void *b) {
 
 static int print_alignments(FILE *out, sw_bank *bank, const uint8_t *res, size_t total,
                             const uint64_t *offs, const uint32_t *lens, const int32_t *scores,
-                            const fasta_t *lib, size_t k, const char *unit) {
-  uint64_t *order = malloc(lib->n * sizeof(uint64_t));
+                            const fasta_t *lib, size_t asked, const char *unit) {
+  const size_t k = asked < lib->n ? asked : lib->n;
+  const int on_device = asked <= SW_TOP_MAX_K; /* (what -A asked for picks the path) */
+  uint64_t *order = malloc((on_device ? k : lib->n) * sizeof(uint64_t));
   sw_alignment *al = malloc(k * sizeof(sw_alignment));
   size_t cap = k, used = 0;
   if (!order || !al) {
@@ -133,14 +136,22 @@ static int print_alignments(FILE *out, sw_bank *bank, const uint8_t *res, size_t
     free(al);
     return 3;
   }
-  for (size_t i = 0; i < lib->n; ++i) order[i] = i;
-  g_sort_scores = scores;
-  qsort(order, lib->n, sizeof(uint64_t), by_score);
-  for (size_t i = 0; i < k; ++i) cap += 2 * (size_t)lens[order[i]]; /* ops a path can have */
-  uint32_t *cig = malloc(cap * sizeof(uint32_t));
-  sw_status st = cig ? sw_align_hits(bank, res, total, offs, lens, NULL, lib->n, order, k, al, cig,
-                                     cap, &used)
-                     : SW_ERR_NOMEM;
+  sw_status st = SW_OK;
+  if (on_device) { /* k <= lib->n and no threshold: every slot is a hit */
+    st = sw_top_hits(bank, scores, NULL, lib->n, 1, k, INT32_MIN, order, NULL, NULL, NULL);
+  } else {
+    for (size_t i = 0; i < lib->n; ++i) order[i] = i;
+    g_sort_scores = scores;
+    qsort(order, lib->n, sizeof(uint64_t), by_score);
+  }
+  uint32_t *cig = NULL;
+  if (st == SW_OK) {
+    for (size_t i = 0; i < k; ++i) cap += 2 * (size_t)lens[order[i]]; /* ops a path can have */
+    cig = malloc(cap * sizeof(uint32_t));
+    st = cig ? sw_align_hits(bank, res, total, offs, lens, NULL, lib->n, order, k, al, cig, cap,
+                             &used)
+             : SW_ERR_NOMEM;
+  }
   if (st != SW_OK) {
     fprintf(stderr, "swbank: %s: %s\n", sw_status_string(st), sw_last_error(bank));
   } else {
@@ -301,8 +312,7 @@ int main(int argc, char **argv) {
       fprintf(out, "%s score: %d\n", nm, scores[k]);
   }
   if (nalign > 0 && lib.n) {
-    int rc = print_alignments(out, bank, res, total, offs, lens, scores, &lib,
-                              (size_t)nalign < lib.n ? (size_t)nalign : lib.n,
+    int rc = print_alignments(out, bank, res, total, offs, lens, scores, &lib, (size_t)nalign,
                               protein ? "aa" : "nt");
     if (rc) {
       if (opath) fclose(out);

@@ -1,0 +1,121 @@
+// swbank_top.hip — the k best hits of every row of a score matrix (include/swbank.h "the k best
+// hits"): the two ABI entries.  The kernels are in swbank_ktop.hip.
+#include "swbank_bank.h"
+
+namespace {
+
+// The arguments both entries refuse; nullptr when they are fine.
+const char* bad_args(const void* scores, const void* hits, size_t n, size_t nq, size_t k) {
+  if (!scores || !hits) return "null scores or hits";
+  if (n == 0 || nq == 0 || k == 0) return "n, nq and k must be positive";
+  if (k > SW_TOP_MAX_K) return "k > SW_TOP_MAX_K";
+  if (n > 0x100000000ull) return "a row holds <= 2^32 scores";
+  if (n > SIZE_MAX / nq || k > SIZE_MAX / nq) return "nq x n or nq x k overflows size_t";
+  if (nq > SIZE_MAX / (swk_top_state_words() * sizeof(unsigned long long)))
+    return "nq overflows the select's state";
+  return nullptr;
+}
+
+// The selection on `hs`, ordered after the previous call's use of the bank's scratch (ev_top).
+sw_status select_on(sw_bank* b, const int32_t* d_scores, const uint64_t* d_ids, size_t n, size_t nq,
+                    size_t k, int32_t min_score, uint64_t* d_hits, int32_t* d_hit_scores,
+                    uint64_t* d_hit_ids, uint32_t* d_counts, hipStream_t hs) {
+  HIPOK(b, b->top_state.reserve(nq * swk_top_state_words()));
+  HIPOK(b, b->top_keys.reserve(nq * k));
+  if (!b->ev_top) HIPOK(b, hipEventCreateWithFlags(&b->ev_top, hipEventDisableTiming));
+  else HIPOK(b, hipStreamWaitEvent(hs, b->ev_top, 0));
+  Timed t{b, hs};
+  sw_status st = t.begin();
+  if (st != SW_OK) {
+    t.drop();
+    return st;
+  }
+  const hipError_t e = swk_top_hits(d_scores, d_ids, n, nq, k, min_score, b->top_state.p,
+                                    b->top_keys.p, d_hits, d_hit_scores, d_hit_ids, d_counts, hs);
+  // whatever was launched uses the scratch: the next call is ordered after it in any case
+  const hipError_t er = hipEventRecord(b->ev_top, hs);
+  if (e != hipSuccess || er != hipSuccess) {
+    t.drop();
+    HIPOK(b, e);
+    HIPOK(b, er);
+  }
+  if ((st = t.end()) != SW_OK) {
+    t.drop();
+    return st;
+  }
+  snprintf(b->last_kernel, sizeof(b->last_kernel), "top k=%zu nq=%zu n=%zu", k, nq, n);
+  return SW_OK;
+}
+
+}  // namespace
+
+extern "C" sw_status sw_top_hits_device(sw_bank* b, const int32_t* d_scores, const uint64_t* d_ids,
+                                        size_t n, size_t nq, size_t k, int32_t min_score,
+                                        uint64_t* d_hits, int32_t* d_hit_scores,
+                                        uint64_t* d_hit_ids, uint32_t* d_counts, void* stream) {
+  DevGuard dev_guard(b);  // on the bank's device; the caller's is restored on return (ABI 6)
+  if (!b) return SW_ERR_ARG;
+  if (const char* why = bad_args(d_scores, d_hits, n, nq, k))
+    return fail(b, SW_ERR_ARG, "sw_top_hits_device: %s", why);
+  if (b->is_multi()) {  // on the root device, where the multi-device calls leave the scores
+    sw_bank* r = b->kids[0];
+    const sw_status st = sw_top_hits_device(r, d_scores, d_ids, n, nq, k, min_score, d_hits,
+                                            d_hit_scores, d_hit_ids, d_counts,
+                                            stream ? stream : r->stream);
+    if (st != SW_OK) return fail(b, st, "device %d: %s", r->device, r->err);
+    snprintf(b->last_kernel, sizeof(b->last_kernel), "%s", r->last_kernel);
+    return SW_OK;
+  }
+  // a hand-off fault latched by an earlier device call is returned before anything runs
+  if (const sw_status fs = take_fault(b, 0); fs != SW_OK) return fs;
+  HIPOK(b, hipSetDevice(b->device));
+  return select_on(b, d_scores, d_ids, n, nq, k, min_score, d_hits, d_hit_scores, d_hit_ids,
+                   d_counts, stream ? reinterpret_cast<hipStream_t>(stream) : b->stream);
+}
+
+extern "C" sw_status sw_top_hits(sw_bank* b, const int32_t* scores, const uint64_t* ids, size_t n,
+                                 size_t nq, size_t k, int32_t min_score, uint64_t* hits,
+                                 int32_t* hit_scores, uint64_t* hit_ids, uint32_t* counts) {
+  DevGuard dev_guard(b);  // on the bank's device; the caller's is restored on return (ABI 6)
+  if (!b) return SW_ERR_ARG;
+  if (const char* why = bad_args(scores, hits, n, nq, k))
+    return fail(b, SW_ERR_ARG, "sw_top_hits: %s", why);
+  if (nq > SIZE_MAX / sizeof(uint64_t) / std::max(n, k))
+    return fail(b, SW_ERR_ARG, "sw_top_hits: nq x n or nq x k bytes overflow size_t");
+  if (b->is_multi()) {  // on the root device
+    sw_bank* r = b->kids[0];
+    const sw_status st =
+        sw_top_hits(r, scores, ids, n, nq, k, min_score, hits, hit_scores, hit_ids, counts);
+    if (st != SW_OK) return fail(b, st, "device %d: %s", r->device, r->err);
+    snprintf(b->last_kernel, sizeof(b->last_kernel), "%s", r->last_kernel);
+    return SW_OK;
+  }
+  HIPOK(b, hipSetDevice(b->device));
+  hipStream_t hs = b->stream;
+  // the previous call (on any stream) is done with the buffers before they are refilled
+  if (b->ev_top) HIPOK(b, hipStreamWaitEvent(hs, b->ev_top, 0));
+  HIPOK(b, b->top_scores.reserve(nq * n));
+  HIPOK(b, b->top_hits.reserve(nq * k));
+  if (hit_scores) HIPOK(b, b->top_hsc.reserve(nq * k));
+  if (counts) HIPOK(b, b->top_cnt.reserve(nq));
+  HIPOK(b, hipMemcpyAsync(b->top_scores.p, scores, nq * n * sizeof(int32_t),
+                          hipMemcpyHostToDevice, hs));
+  const sw_status st =
+      select_on(b, b->top_scores.p, nullptr, n, nq, k, min_score, b->top_hits.p,
+                hit_scores ? b->top_hsc.p : nullptr, nullptr, counts ? b->top_cnt.p : nullptr, hs);
+  if (st != SW_OK) return st;
+  HIPOK(b, hipMemcpyAsync(hits, b->top_hits.p, nq * k * sizeof(uint64_t), hipMemcpyDeviceToHost,
+                          hs));
+  if (hit_scores)
+    HIPOK(b, hipMemcpyAsync(hit_scores, b->top_hsc.p, nq * k * sizeof(int32_t),
+                            hipMemcpyDeviceToHost, hs));
+  if (counts)
+    HIPOK(b, hipMemcpyAsync(counts, b->top_cnt.p, nq * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                            hs));
+  HIPOK(b, hipEventRecord(b->ev_top, hs));  // (the copies read the result buffers)
+  HIPOK(b, hipStreamSynchronize(hs));
+  if (hit_ids)
+    for (size_t i = 0; i < nq * k; ++i)
+      hit_ids[i] = hits[i] == SW_HIT_NONE ? SW_HIT_NONE : ids ? ids[hits[i]] : hits[i];
+  return SW_OK;
+}

@@ -46,6 +46,7 @@ EXPORTS = (
     "sw_query_count", "sw_score_batch_device_range", "sw_bank_counters",
     "sw_bank_counters_ex", "sw_bank_sync", "sw_score_batch_device_multi",
     "sw_align_hits", "sw_align_hits_device", "sw_cigar_string",
+    "sw_top_hits", "sw_top_hits_device",
 )
 ABI_VERSION = 6
 COUNTERS = ("stream_calls", "stream_reruns", "stream_declined", "chunked_calls", "device_sorts",
@@ -56,6 +57,9 @@ MAX_DEVICES = 16
 CIGAR_M, CIGAR_I, CIGAR_D = 0, 1, 2          # BAM codes: I consumes query only, D target only
 ALIGN_EMPTY, ALIGN_NO_PATH = 1, 2            # sw_alignment.flags
 RECORD_BYTES, RECORD_MAX_BASES = 64, 232
+TOP_MAX_K = 4096                             # SW_TOP_MAX_K: the largest k of the top-hits calls
+HIT_NONE = 0xFFFFFFFFFFFFFFFF                # SW_HIT_NONE: a hit slot past the row's count
+INT32_MIN = -(1 << 31)                       # min_score: no threshold; the score of such a slot
 
 
 class SwbankError(RuntimeError):
@@ -204,6 +208,8 @@ def lib() -> ctypes.CDLL:
         "sw_align_hits": (i32, [P, P, sz, P, P, P, sz, P, sz, P, P, sz, P]),
         "sw_align_hits_device": (i32, [P, P, P, P, P, sz, u32, P, sz, P, P, u32, P]),
         "sw_cigar_string": (sz, [P, sz, P, sz]),
+        "sw_top_hits": (i32, [P, P, P, sz, sz, sz, i32, P, P, P, P]),
+        "sw_top_hits_device": (i32, [P, P, P, sz, sz, sz, i32, P, P, P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -506,6 +512,48 @@ class ScoreBank:
                                                d_lens or None, d_ids or None, n, max_len,
                                                d_hits or None, n_hits, d_out or None,
                                                d_cigar or None, cigar_stride, stream or None))
+
+    # the k best hits of a score matrix
+    def top_hits(self, scores: np.ndarray, k: int, ids: Optional[np.ndarray] = None,
+                 min_score: Optional[int] = None):
+        """sw_top_hits: the k best of every row of `scores` (1-D: one row; 2-D [nq, n]), score
+        descending, then batch position ascending, among the scores >= min_score (None: all).
+        Returns (hits uint64, hit_scores int32, hit_ids uint64, counts uint32): [k] and a scalar
+        count for 1-D scores, [nq, k] and [nq] for 2-D; slots past a row's count hold HIT_NONE /
+        INT32_MIN / HIT_NONE."""
+        s = np.ascontiguousarray(scores, dtype=np.int32)
+        if s.ndim not in (1, 2):
+            raise ValueError("scores: 1-D, or 2-D [nq, n]")
+        rows = s.reshape(1, -1) if s.ndim == 1 else s
+        nq, n = rows.shape
+        idv = None
+        if ids is not None:
+            idv = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+            if idv.size != n:
+                raise ValueError(f"{idv.size} ids for {n} targets")
+        kk = max(int(k), 1)
+        hits = np.empty((nq, kk), np.uint64)
+        hsc = np.empty((nq, kk), np.int32)
+        hid = np.empty((nq, kk), np.uint64)
+        cnt = np.empty(nq, np.uint32)
+        self._check(lib().sw_top_hits(self._h, _p(rows), _p(idv) if idv is not None else None, n,
+                                      nq, k, INT32_MIN if min_score is None else min_score,
+                                      _p(hits), _p(hsc), _p(hid), _p(cnt)))
+        if s.ndim == 1:
+            return hits[0], hsc[0], hid[0], cnt[0]
+        return hits, hsc, hid, cnt
+
+    def top_hits_device(self, d_scores: int, n: int, k: int, d_hits: int, nq: int = 1,
+                        d_ids: int = 0, min_score: Optional[int] = None, d_hit_scores: int = 0,
+                        d_hit_ids: int = 0, d_counts: int = 0, stream: int = 0):
+        """sw_top_hits_device: device pointers (ints); d_scores holds nq rows of n int32 scores,
+        d_hits receives nq x k uint64 batch positions (the hit list align_hits_device takes),
+        d_hit_scores / d_hit_ids / d_counts (optional) nq x k int32, nq x k uint64, nq uint32.
+        Async on `stream` (0: the bank's own stream; sync() before reading)."""
+        self._check(lib().sw_top_hits_device(self._h, d_scores or None, d_ids or None, n, nq, k,
+                                             INT32_MIN if min_score is None else min_score,
+                                             d_hits or None, d_hit_scores or None,
+                                             d_hit_ids or None, d_counts or None, stream or None))
 
     def counters(self) -> dict:
         """sw_bank_counters: feeder / fallback counts since the bank was created."""
