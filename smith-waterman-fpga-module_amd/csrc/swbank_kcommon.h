@@ -808,14 +808,26 @@ __device__ __forceinline__ void report_fault(uint32_t* fault, uint32_t bit) {
 typedef __attribute__((address_space(3))) void* lds_void_ptr;
 typedef __attribute__((address_space(1))) void* glob_void_ptr;
 
-// C columns x 64 lanes x uint2 (4 KB for C = 8) global -> LDS by one wave: C / 2 LDS-DMA
-// instructions of 16 B per lane, lane-linear (the source layout is already [col][lane]).
+// Row stride of the tile kernel's LDS hand-off rows (ring slots and the previous segment's edge
+// rows), in uint2: 64 lanes and one more entry, which holds the constant row -1 boundary in the
+// rows wave 0 reads when there is no previous segment.  One stride for every
+// row a wave reads or writes in the column loop, so each access carries its column as the
+// instruction's offset.
+#define SWK_RING_ROW 65
+
+// C columns x 64 lanes x uint2 (4 KB for C = 8) global -> LDS by one wave, into rows
+// SWK_RING_ROW entries apart: 2 C LDS-DMA instructions of 4 B per lane, half a row each (the
+// source layout is [col][lane]; a 16-byte transfer would span two rows, which are no longer
+// adjacent, and a row starts on an 8-byte boundary only).
 template <int C = 8>
 __device__ __forceinline__ void dma_edge_chunk(const uint2* src, uint2* dst, int lane) {
+  const uint32_t* s = reinterpret_cast<const uint32_t*>(src) + lane;
 #pragma unroll
-  for (int q = 0; q < C / 2; ++q)
-    __builtin_amdgcn_global_load_lds((glob_void_ptr)(src + q * 128 + lane * 2),
-                                     (lds_void_ptr)(dst + q * 128), 16, 0, 0);
+  for (int q = 0; q < 2 * C; ++q)
+    __builtin_amdgcn_global_load_lds(
+        (glob_void_ptr)(s + q * 64),
+        (lds_void_ptr)(reinterpret_cast<uint32_t*>(dst + (q >> 1) * SWK_RING_ROW) + (q & 1) * 64),
+        4, 0, 0);
 }
 
 // Chunk count of a tile (uniform), from the lengths alone.

@@ -33,11 +33,14 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
   const int W = __builtin_amdgcn_readfirstlane(blockDim.x >> 6);
   const bool seg_in = a.edge_in != nullptr, seg_out = a.edge_out != nullptr;
   uint32_t* bestsh = smem + (PAIR ? a.PS / 4 : 0);               // W x 128 words
-  uint2* bnd = reinterpret_cast<uint2*>(bestsh + W * SWB_TILE);  // row -1 boundary
-  uint2* sink = bnd + 64;                                        // last wave's bottom row
-  uint2* ein = sink + (seg_out ? C * 64 : 64);                   // previous segment, 2 x 8 cols
-  uint2* ring = ein + (seg_in ? 2 * C * 64 : 0);
-  uint8_t* prof = reinterpret_cast<uint8_t*>(ring + (size_t)(W > 1 ? W - 1 : 0) * 2 * C * 64);
+  // hand-off rows of RS = 65 uint2 (tile_ring_entries): the previous segment's edge rows (2
+  // slots of C), then the ring, 2 slots of C rows per wave boundary.  Entry 64 of the first
+  // slot's rows is the constant row -1 boundary; the last wave's bottom row goes into the slot
+  // it is reading (W = 1: one slot, of which wave 0 reads entry 64 and writes lanes 0-63)
+  constexpr int RS = SWK_RING_ROW;
+  uint2* ein = reinterpret_cast<uint2*>(bestsh + W * SWB_TILE);  // previous segment, 2 x C cols
+  uint2* ring = ein + (seg_in ? 2 * C * RS : 0);
+  uint8_t* prof = reinterpret_cast<uint8_t*>(ring + (size_t)(W > 1 ? 2 * (W - 1) : 1) * C * RS);
 
   size_t n = a.n;
   const uint32_t* idx = a.idx;
@@ -198,8 +201,10 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
   const f16x2 NOE2 = as_f16x2(as_u16x2(a.f16_noe)), NE2 = as_f16x2(as_u16x2(a.f16_ne)),
               NO2 = as_f16x2(as_u16x2(a.f16_no));
   if (wave == 0) {
-    bnd[lane] = F16 ? make_uint2(0u, GOTOH ? 0u : as_u32(as_u16x2(NOE2)))
-                    : make_uint2(S | (S << 16), 0u);
+    // (entry 64 of the first ring slot's C rows: no lane's own entry, so no wave overwrites it)
+    if (lane < C)
+      ring[lane * RS + 64] = F16 ? make_uint2(0u, GOTOH ? 0u : as_u32(as_u16x2(NOE2)))
+                                 : make_uint2(S | (S << 16), 0u);
     if (seg_in)  // the previous segment's bottom row of chunk 0
       dma_edge_chunk<C>(a.edge_in + (size_t)(MQ ? unit : tile) * a.ecols * 64, ein, lane);
   }
@@ -282,11 +287,11 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
   }
   (void)pA0; (void)pA1; (void)pw; (void)acur; (void)wofs;
 
-  // branch-free hand-off: wave 0 reads the top boundary (constant, stride 0, or the previous
-  // segment's row), the last wave writes into an LDS sink (branches inside the column loop
-  // split it into blocks and LLVM then sinks the H updates across columns, blowing up
-  // register pressure)
-  const int istride = (wave > 0 || seg_in) ? 64 : 0, ostride = (wave < W - 1 || seg_out) ? 64 : 0;
+  // branch-free hand-off: wave 0 reads the top boundary (the constant entry 64 of the first
+  // slot's rows, every lane the same address, or the previous segment's rows), the last wave
+  // writes into the slot it is reading (branches inside the column loop split it into blocks
+  // and LLVM then sinks the H updates across columns, blowing up register pressure).  Every
+  // row is RS entries from the next, so a column's address is an instruction offset.
   const uint32_t pbase = (uint32_t)wave * R;
   const uint32_t padc = a.pad;
   // BAL hand-off of one wave's column state {H, T of its R rows, the diagonal H above, best}
@@ -296,12 +301,15 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
   // sc1 loads).  The consumer's tail is its last visit and the producer's head its first, so
   // the flag is normally long set; the poll is bounded (poll_limit, about 4 s) and a time-out
   // marks the launch's fault word (the host fails the call) rather than hanging.
-  // (the state addresses go through an opaque copy: loop-invariant, LLVM would otherwise hoist
-  // all 2R + 2 of them out of the phase loop, 2 VGPRs each, and spill)
+  // (the state addresses start from an opaque copy of the lane number: loop-invariant, LLVM
+  // would otherwise hoist all 2R + 2 of them out of the phase loop, 2 VGPRs each, and spill;
+  // with the copy taken of the finished base address instead, that base alone was hoisted and
+  // spilled, 2 x 8 B of scratch per lane)
   int bal_pend = 0;  // BAL: phases until the head's flag goes out (0: none pending)
   const auto bal_store = [&](int g_to) {
-    uint32_t* sp = a.bal_state + ((size_t)g_to * W + wave) * (2 * R + 2) * 64 + lane;
-    asm volatile("" : "+v"(sp));
+    uint32_t ol = (uint32_t)lane;
+    asm volatile("" : "+v"(ol));
+    uint32_t* sp = a.bal_state + ((size_t)g_to * W + wave) * (2 * R + 2) * 64 + ol;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       __hip_atomic_store(sp + r * 64, as_u32(Hl[r]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -336,8 +344,9 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
     }
     if (it == a.poll_limit && lane == 0) report_fault(a.fault, SWK_FAULT_BAL);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const uint32_t* sp = a.bal_state + ((size_t)blockIdx.x * W + wave) * (2 * R + 2) * 64 + lane;
-    asm volatile("" : "+v"(sp));
+    uint32_t ol = (uint32_t)lane;
+    asm volatile("" : "+v"(ol));
+    const uint32_t* sp = a.bal_state + ((size_t)blockIdx.x * W + wave) * (2 * R + 2) * 64 + ol;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       Hl[r] = as_u16x2(__hip_atomic_load(sp + r * 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
@@ -438,11 +447,16 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
       if (seg_in && wave == 0 && (last ? nunit < nunits : (MQ ? unit : tile) < nunits))
         dma_edge_chunk<C>(a.edge_in + ((size_t)(last ? nunit : MQ ? unit : tile) * a.ecols +
                                     (size_t)(last ? 0 : c + 1) * C) * 64,
-                       ein + (size_t)((g + 1) & 1) * C * 64, lane);
-      const uint2* rin = wave > 0 ? ring + ((size_t)((wave - 1) * 2 + slot) * C) * 64 + lane
-                                  : (seg_in ? ein + (size_t)slot * C * 64 : bnd) + lane;
-      uint2* rout = wave < W - 1 ? ring + ((size_t)(wave * 2 + slot) * C) * 64 + lane
-                                 : sink + lane;
+                       ein + (size_t)((g + 1) & 1) * C * RS, lane);
+      uint2* rin = wave > 0 ? ring + ((size_t)((wave - 1) * 2 + slot) * C) * RS + lane
+                   : seg_in ? ein + (size_t)slot * C * RS + lane
+                            : ring + 64;
+      // the last wave's sink: column jj's entry of the slot it reads was consumed a column
+      // earlier (rv runs one column ahead), the producer writes the other slot in this phase
+      // and refills this one only after the phase barrier
+      uint2* rout = wave < W - 1 ? ring + ((size_t)(wave * 2 + slot) * C) * RS + lane
+                    : W > 1      ? rin
+                                 : ring + lane;
       uint2 rv = rin[0];
       ProfLookup16<PROF && F16 ? R : 2> lkq;  // f16 profile: the next column's words
       (void)lkq;
@@ -463,7 +477,7 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
         }
         const u16x2 upH = as_u16x2(rv.x);
         u16x2 upX = as_u16x2(rv.y);
-        if (jj + 1 < C) rv = rin[(jj + 1) * istride];  // one column ahead
+        if (jj + 1 < C) rv = rin[(jj + 1) * RS];  // one column ahead
         u16x2 diag = prevUpH;
         prevUpH = upH;
         const uint32_t wlo = jj < 4 ? clo.x : clo.y, whi = jj < 4 ? chi.x : chi.y;
@@ -615,7 +629,7 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
         // pin the running max once per column: otherwise LLVM re-associates the max over the
         // whole phase into a tree and keeps every M live
         asm volatile("" : "+v"(best));
-        rout[jj * ostride] = make_uint2(as_u32(Hl[R - 1]), as_u32(upX));
+        rout[jj * RS] = make_uint2(as_u32(Hl[R - 1]), as_u32(upX));
       }
       if constexpr (PAIR && TRIM) {
         if (trimmed) {  // the next chunk's column 0, read ahead as at a chunk's end
@@ -629,7 +643,7 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
       if (seg_out && wave == W - 1) {  // this segment's bottom row -> the next segment
         uint2* dst = a.edge_out + ((size_t)(MQ ? unit : tile) * a.ecols + (size_t)c * C) * 64 + lane;
 #pragma unroll
-        for (int jj = 0; jj < C; ++jj) dst[jj * 64] = sink[jj * 64 + lane];
+        for (int jj = 0; jj < C; ++jj) dst[jj * 64] = rout[jj * RS];
       }
       if (last) {
         // BAL: the first visit is a head when the range ends inside a tile
@@ -743,14 +757,21 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
 #endif
 }
 
+// uint2 entries of score_kernel's hand-off rows: 2 slots of C rows per wave boundary (one slot
+// for a single wave: its boundary entries and its sink) and 2 slots of edge rows when a
+// previous segment feeds wave 0, every row SWK_RING_ROW entries.  The headline launch (W = 4,
+// C = 8, one segment): 48 x 65 x 8 = 24,960 B, with 2,048 B of bests and the 12,800-byte pair
+// table 39,808 B per workgroup, 4 workgroups per CU.
+static size_t tile_ring_entries(int W, int C, bool seg_in) {
+  return (size_t)((W > 1 ? 2 * (W - 1) : 1) + (seg_in ? 2 : 0)) * C * SWK_RING_ROW;
+}
+
 template <int R, int RB, bool COL0, bool PROF, bool GOTOH, bool F16, bool PAIR = false,
           bool MQ = false, bool STREAM = false, int C = 8, bool BAL = false, bool TRIM = false>
 static hipError_t launch_score(const ScoreArgs& a, int W, uint32_t prof_bytes, hipStream_t st,
                                unsigned bal_grid = 0) {
   const size_t ntiles = (a.n + SWB_TILE - 1) / SWB_TILE * (MQ ? a.nq : 1);  // units
-  const size_t lds = (size_t)W * SWB_TILE * 4 +
-                     (size_t)(64 + (a.edge_out ? C * 64 : 64) + (a.edge_in ? 2 * C * 64 : 0) +
-                              (W > 1 ? W - 1 : 0) * 2 * C * 64) * 8 +
+  const size_t lds = (size_t)W * SWB_TILE * 4 + tile_ring_entries(W, C, a.edge_in != nullptr) * 8 +
                      (PROF ? prof_bytes : 0) + (PAIR ? a.PS : 0) + (STREAM ? 256 : 0);
   auto fn = &score_kernel<R, RB, COL0, PROF, GOTOH, F16, PAIR, MQ, STREAM, C, BAL, TRIM>;
   static bool attr_set = false;
@@ -917,7 +938,7 @@ extern "C" unsigned swk_bal_slots(int W, uint32_t PS, int trim) {
   if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) !=
       hipSuccess)
     return 0;
-  const size_t lds = (size_t)W * SWB_TILE * 4 + (size_t)(64 + 64 + (W - 1) * 2 * 8 * 64) * 8 + PS;
+  const size_t lds = (size_t)W * SWB_TILE * 4 + swk::tile_ring_entries(W, 8, false) * 8 + PS;
   int dev = 0, cus = 0;
   if (hipGetDevice(&dev) != hipSuccess) return 0;
   const int occ = swk::cached_occupancy(fn, 64 * W, lds, dev, &cus);
