@@ -41,6 +41,9 @@ is max(0, x) as for the add; scripts/ubench/fma_opsel.hip checks both and the is
 equals v_pk_add_f16's).  So a profile row costs 7.5 VALU (Gotoh) / 5.5 (merged) per 2 cells like
 the DNA letter-pair table, without a table per letter pair.
 
+Skewed merged pair rows (SWK_F16SKEW_F/M/L, skew_pair_block below): cells in anti-diagonal
+frames, 5 VALU per row with the letter-pair table holding s + 2e.
+
 No two dependent packed (VOP3P) ops are adjacent (gfx950 needs a wait state between them;
 v_perm_b32 -> VOP3P needs none), so a block needs no s_nop inside; LLVM adds one wait state
 per asm block.  D alternates between Da/Db by row parity.  The last block of a column ends
@@ -149,6 +152,45 @@ def pair_gotoh_block(first, last, nrows=8):
     return out + gotoh_block("pair", last, nrows)
 
 
+def skew_pair_block(first, last, nrows=8):
+    """Pair-profile block in anti-diagonal frames (DNA, merged gaps, DESIGN 3.1 "skewed rows"):
+    cell (i, j) is held with the offset c_k = e (k - 1), k = i + j, so the gap extension is
+    paid by the frame and a row is 4 VALU, plus one add and one max3 per two rows for the best:
+
+        A'  = Hl(old) + p            next row's A = H^(i-1,j-1) + (s + 2e)   (no clamp)
+        T~  = max3(AO, Tup, Tl) -> Tl   (= G + c_k: what the right and lower cells read)
+        AO' = A' + (-o)              next row's A - o
+        H^  = max3(T~, A, c_k)  -> Hl   c_k: the frame's floor (H = 0), an SGPR per row
+        best = best + 2e             even rows: the running best moved two frames on
+        best = max3(best, H^(i-1,j) new, H^(i,j-1) old)  odd rows, before row i's H^ is written
+
+    The first block forms row 0's A and A - o from dg + pw and moves the best from the last
+    pair of the previous column to the first of this one (e2f = (3 - rows per wave) e).  AO
+    runs one row ahead through the blocks like Da; no two dependent packed ops are adjacent."""
+    out = []
+    for i in range(nrows):
+        dcur, dnext = ("%[Da]", "%[Db]") if i % 2 == 0 else ("%[Db]", "%[Da]")
+        up = "%[up]" if i == 0 else f"%[t{i - 1}]"
+        final = last and i == nrows - 1
+        nd = f"v_pk_add_f16 {dnext}, %[h{i}], %[p{i}]"
+        ao = f"v_pk_add_f16 %[AO], {dnext}, %[no]"
+        tt = f"v_pk_maximum3_f16 %[t{i}], %[AO], {up}, %[t{i}]"
+        hh = f"v_pk_maximum3_f16 %[h{i}], %[t{i}], {dcur}, %[c{i}]"
+        if i % 2 == 0:
+            step = "%[e2f]" if first and i == 0 else "%[e2]"
+            bt = f"v_pk_add_f16 %[best], %[best], {step}"
+            if first and i == 0:
+                out += ["v_pk_add_f16 %[Da], %[dg], %[pw]", nd,
+                        "v_pk_add_f16 %[AO], %[Da], %[no]", bt, tt, ao, hh]
+            else:
+                out += [nd, tt, ao, bt, hh]
+        else:
+            bb = f"v_pk_maximum3_f16 %[best], %[best], %[h{i - 1}], %[h{i}]"
+            out += [tt, bb, hh] if final else [nd, bb, tt, ao, hh]
+    assert nrows % 2 == 0
+    return out
+
+
 def fmt(lines):
     return "".join(f'  "{ln}\\n\\t" \\\n' for ln in lines) + '  ""\n'
 
@@ -180,6 +222,9 @@ def main():
     parts.append("#define SWK_F16PAIRG_F \\\n" + fmt(pair_gotoh_block(True, False)))
     parts.append("#define SWK_F16PAIRG_M \\\n" + fmt(pair_gotoh_block(False, False)))
     parts.append("#define SWK_F16PAIRG_L \\\n" + fmt(pair_gotoh_block(False, True)))
+    parts.append("#define SWK_F16SKEW_F \\\n" + fmt(skew_pair_block(True, False)))
+    parts.append("#define SWK_F16SKEW_M \\\n" + fmt(skew_pair_block(False, False)))
+    parts.append("#define SWK_F16SKEW_L \\\n" + fmt(skew_pair_block(False, True)))
     # mode F (profile words {s, 1.0}: one packed FMA per row, no lookup), 8-row blocks
     for last in (0, 1):
         parts.append(f"#define SWK_F16M_F_Z0_L{last} \\\n" + fmt(merged_block("F", 0, last)))

@@ -60,8 +60,9 @@ extern "C" hipError_t swk_launch_score(int R, int RB, int col0, int prof, int go
                                        const uint32_t* nidx, uint32_t idx_base,
                                        const uint32_t* ident, int pair, uint32_t pS1,
                                        uint32_t pS2, uint32_t ulen, uint32_t ustride, uint32_t nq,
-                                       uint32_t qwords, size_t sstride, hipStream_t st);
-extern "C" unsigned swk_bal_slots(int W, uint32_t PS, int trim);
+                                       uint32_t qwords, size_t sstride, hipStream_t st,
+                                       const uint32_t* skew_tab = nullptr);
+extern "C" unsigned swk_bal_slots(int W, uint32_t PS, int trim, int skew = 0);
 extern "C" unsigned swk_wave_half_grid(int gotoh, uint32_t prof_bytes, int W);
 extern "C" hipError_t swk_bal_plan_uniform(void* plan, uint32_t ntiles, uint32_t K, uint32_t G,
                                            hipStream_t st);
@@ -75,7 +76,8 @@ extern "C" hipError_t swk_launch_pair_bal(const uint8_t* res, const uint64_t* of
                                           const uint32_t* nidx, const uint32_t* ident,
                                           const void* plan, uint32_t* fault, uint32_t poll_limit,
                                           uint32_t stall, int trim, uint32_t packed,
-                                          const uint32_t* sidx, hipStream_t st);
+                                          const uint32_t* sidx, hipStream_t st,
+                                          const uint32_t* skew_tab = nullptr);
 extern "C" hipError_t swk_best_hit(const int32_t* scores, const uint64_t* ids, size_t n,
                                    unsigned long long* key, uint64_t* out, uint64_t* out_index,
                                    hipStream_t st);
@@ -403,6 +405,13 @@ struct sw_bank {
   // PAIR variant; pair_bytes = 0 when the query does not qualify
   DevBuf<uint32_t> qpair;
   uint32_t pair_bytes = 0, pS1 = 0, pS2 = 0;
+  // the skewed rows of the merged pair kernel: a second pair table holding s + 2e
+  // (same layout; rows past the query -skew_pad + 2e) and the frames' floors skew_ctab[k + 2] =
+  // c_k = e (k - 1), skew_entries words.  skew_neg: the most negative value a skewed column
+  // forms; skew_entries = 0 when the query has no merged pair table
+  DevBuf<uint32_t> qpair_skew, skew_ctab;
+  uint32_t skew_entries = 0;
+  int32_t skew_neg = 0;
   DevBuf<uint32_t> fb_idx, fb_cnt;  // pairs an optimistic f16 pass re-scores in u16
   // int32 re-score of the pairs past the 16-bit lanes (built on first use per query):
   // [strip][letter 0..pad][lane] 4 x int16, strips of 256 rows; per-wave scratch rows

@@ -187,6 +187,8 @@ extern "C" void sw_bank_destroy(sw_bank* b) {
   b->mqtab16.release();
   b->mqpair.release();
   b->qpair.release();
+  b->qpair_skew.release();
+  b->skew_ctab.release();
   b->stage.release();
   if (b->ev_ready) (void)hipEventDestroy(b->ev_ready);
   if (b->ev_used) (void)hipEventDestroy(b->ev_used);
@@ -522,14 +524,19 @@ static void pair_strides(uint32_t NR, uint32_t& pS1, uint32_t& pS2) {
 // The letter-pair table of query rows [r0, r0 + NR) (the PAIR tile kernel, DNA merged f16):
 // slot (a, b) holds word k = {s(q_{r0+k+1}, a), s(q_{r0+k+1}, b)} (f16 halves; rows past the
 // query -2048) and the row-r0 word 4 bytes before it.
+// add / pad: the skewed rows' table holds s + add (add = 2e) and pad + add in rows past the query
+// (the unskewed kernel's: s, -2048).
 static std::vector<uint32_t> pair_table(const uint8_t* q, int qlen, int r0, uint32_t NR,
-                                        const int8_t* m, int A, uint32_t pS1, uint32_t pS2) {
+                                        const int8_t* m, int A, uint32_t pS1, uint32_t pS2,
+                                        int add = 0, int pad = -2048) {
   const uint32_t bytes = 16 + 4 * pS1 + 4 * pS2 + 4 * NR;
-  std::vector<uint32_t> t(bytes / 4, 0xBC00BC00u);
+  const uint32_t padw = (uint32_t)f16_score_bits(pad + add) * 0x10001u;
+  std::vector<uint32_t> t(bytes / 4, padw);
   auto word = [&](int r, int x, int y) -> uint32_t {  // row r of the segment, letters x, y
-    if (r0 + r >= qlen) return 0xBC00BC00u;
+    if (r0 + r >= qlen) return padw;
     const int c = q[r0 + r];
-    return (uint32_t)f16_score_bits(m[c * A + x]) | (uint32_t)f16_score_bits(m[c * A + y]) << 16;
+    return (uint32_t)f16_score_bits(m[c * A + x] + add) |
+           (uint32_t)f16_score_bits(m[c * A + y] + add) << 16;
   };
   for (int x = 0; x < A; ++x)
     for (int y = 0; y < A; ++y) {
@@ -715,6 +722,22 @@ sw_status prepare(sw_bank* b) {
       tpair.insert(tpair.end(), t.begin(), t.end());
     }
   }
+  // The skewed rows of the merged pair kernel: the same table with s + 2e, rows
+  // past the query with a score no H can lift above 0 (H <= max(s) x rows), and the floors
+  // c_k = e (k - 1) of the anti-diagonal frames, word k + 2 (k = -2 ..: the diagonal above a
+  // tile's first cell).  launch() takes them when a batch's values fit f16 with the offsets.
+  std::vector<uint32_t> tskew, tfloor;
+  int skew_neg = 0;
+  if (!tpair.empty() && !gotoh && 2 * e <= 2048) {
+    const int spad = -std::min(2048 - 2 * e, S * std::max(qlen, 1));
+    tskew = pair_table(b->query.data(), qlen, 0, (uint32_t)segs[0].W * R, m, A, pS1, pS2, 2 * e,
+                       spad);
+    tfloor.resize(2048 + 192);
+    for (size_t k = 0; k < tfloor.size(); ++k)
+      tfloor[k] = (uint32_t)f16_score_bits(std::min(2048, e * ((int)k - 3))) * 0x10001u;
+    // the most negative value: A - o in the first frame, A = c_{-2} + min(s, pad) + 2e
+    skew_neg = -3 * e + std::min(smin, spad) + 2 * e - o;
+  }
   // wave-kernel layout of the same query: rows padded to 64K; queries past 1024 rows run as
   // 1024-row segments (K = 16), one table per segment, concatenated
   const auto wave_tables = [&](int wrows, int nsegs, std::vector<uint32_t>& wt,
@@ -788,7 +811,8 @@ sw_status prepare(sw_bank* b) {
   HIPOK(b, hipEventSynchronize(b->ev_ready));
   const size_t nbytes =
       (wt16.size() + wt.size() + st16[0].size() + st[0].size() + st16[1].size() +
-       st[1].size() + st16[2].size() + st[2].size() + tab.size() + tab16.size() + tpair.size()) *
+       st[1].size() + st16[2].size() + st[2].size() + tab.size() + tab16.size() + tpair.size() +
+       tskew.size() + tfloor.size()) *
       4;
   HIPOK(b, b->stage.reserve(nbytes));
   // earlier launches (any stream) must be done reading the tables this upload overwrites
@@ -822,6 +846,12 @@ sw_status prepare(sw_bank* b) {
   HIPOK(b, upload(b->qtab, tab));
   if (f16) HIPOK(b, upload(b->qtab16, tab16));
   if (!tpair.empty()) HIPOK(b, upload(b->qpair, tpair));
+  if (!tskew.empty()) {
+    HIPOK(b, upload(b->qpair_skew, tskew));
+    HIPOK(b, upload(b->skew_ctab, tfloor));
+  }
+  b->skew_entries = tskew.empty() ? 0u : (uint32_t)tfloor.size();
+  b->skew_neg = skew_neg;
   b->pair_bytes = pair_words * 4;  // one segment's table
   b->pS1 = pS1;
   b->pS2 = pS2;

@@ -794,8 +794,14 @@ struct ScoreArgs {
   // honoured) while its codes, offsets and lengths are read at k (a copy of the batch in its
   // visiting order, SWBANK_RAGGED_GATHER)
   const uint32_t* sidx;
+  // (SKEW variants) cells in anti-diagonal frames: ctab[k + 2] = f16_pair(c_k), the
+  // floor c_k = e (k - 1) of frame k = query row + tile column, for k = -2 .. rows + columns + 40
+  // (a wave reads a 40-word slice per chunk with scalar loads); qtab then holds s + 2e.
+  // f16_e2 = f16_pair(2e), f16_e2f = f16_pair((3 - R) e): the running best's frame steps
+  const uint32_t* ctab;
+  uint32_t f16_e2, f16_e2f;
 };
-static_assert(sizeof(ScoreArgs) == 376, "ScoreArgs layout (kernel argument block) changed");
+static_assert(sizeof(ScoreArgs) == 392, "ScoreArgs layout (kernel argument block) changed");
 
 // a hand-off wait ran out: mark the kind's word of the call's fault group (a vector store to
 // host memory, one word per kind so two kinds in one call are both kept; only the host reads

@@ -17,10 +17,13 @@ namespace swk {
 #define SWK_TRIM_BREAK 1
 #endif
 template <int R, int RB, bool COL0, bool PROF, bool GOTOH, bool F16, bool PAIR = false,
-          bool MQ = false, bool STREAM = false, int C = 8, bool BAL = false, bool TRIM = false>
+          bool MQ = false, bool STREAM = false, int C = 8, bool BAL = false, bool TRIM = false,
+          bool SKEW = false>
 __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const ScoreArgs a) {
   static_assert(!BAL || (!MQ && !STREAM && !COL0), "balanced ranges: one query, resident batch");
   static_assert(!TRIM || (BAL && PAIR), "trimmed last chunks: the balanced pair kernel");
+  static_assert(!SKEW || (PAIR && F16 && !GOTOH && !MQ && !STREAM && R == 32 && C == 8),
+                "SKEW: the merged f16 pair rows, one query, resident batch");
   static_assert(!MQ || !PROF, "several queries: row-LUT or pair-table variants");
   static_assert(!STREAM || (!MQ && !PROF), "streamed batches: single-query LUT / pair variants");
   static_assert(C == 8 || (C == 4 && PAIR && !STREAM), "4-column chunks: pair tables only");
@@ -70,7 +73,16 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
   // (a visit's end chunk is the tile's own chunk count, c1 = -1 until the tile's lengths are
   // read; the plan is read once, into SGPRs: a global load at every visit's end stalls the wave)
   int bs = 0, bo = 0, be = 0, bf = 0;
-  if constexpr (BAL) {
+  if constexpr (BAL && SKEW) {
+    // (scalar loads: the plan was written by an earlier kernel; as vector loads LLVM keeps a
+    // VGPR copy of the range live across the column loop, and the skewed column has none to spare)
+    typedef __attribute__((address_space(4))) const uint32_t plan_u32;
+    plan_u32* const pp = reinterpret_cast<plan_u32*>(reinterpret_cast<uintptr_t>(a.bal_plan)) +
+                         (size_t)blockIdx.x * 4;
+    bs = (int)pp[0], bo = (int)pp[1];
+    be = (int)pp[4], bf = (int)pp[5];
+    total = (int)(pp[6] - pp[2]);
+  } else if constexpr (BAL) {
     const uint4 p0 = a.bal_plan[blockIdx.x], p1 = a.bal_plan[blockIdx.x + 1];
     bs = (int)__builtin_amdgcn_readfirstlane(p0.x), bo = (int)__builtin_amdgcn_readfirstlane(p0.y);
     be = (int)__builtin_amdgcn_readfirstlane(p1.x), bf = (int)__builtin_amdgcn_readfirstlane(p1.y);
@@ -89,9 +101,11 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
     } else {
       t = nunits, c0 = 0, c1 = 1;  // no more visits
     }
-    t = __builtin_amdgcn_readfirstlane(t);
-    c0 = __builtin_amdgcn_readfirstlane(c0);
-    c1 = __builtin_amdgcn_readfirstlane(c1);
+    if constexpr (!SKEW) {  // (SKEW: the plan came by scalar loads, all of this is SALU already)
+      t = __builtin_amdgcn_readfirstlane(t);
+      c0 = __builtin_amdgcn_readfirstlane(c0);
+      c1 = __builtin_amdgcn_readfirstlane(c1);
+    }
   };
   if constexpr (BAL) {
   } else if constexpr (STREAM) {
@@ -200,6 +214,34 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
   // f16 encodings of -(o+e), -e, -o (host-computed, so they stay in SGPRs)
   const f16x2 NOE2 = as_f16x2(as_u16x2(a.f16_noe)), NE2 = as_f16x2(as_u16x2(a.f16_ne)),
               NO2 = as_f16x2(as_u16x2(a.f16_no));
+  // SKEW (skewed rows): cell (i, j) of a tile is held in the frame of its
+  // anti-diagonal k = (query row i) + (tile column j): H^ = H + c_k, T~ = G + c_k, c_k = e (k - 1).
+  // ct[k + 2] = c_k (both halves), read with scalar loads; row -1 and column -1 hold H = 0 as
+  // their frames' floors and a T~ far below every floor (-2048: it only ever enters a max)
+  typedef __attribute__((address_space(4))) const uint32_t cst_u32;
+  cst_u32* const ct = reinterpret_cast<cst_u32*>(reinterpret_cast<uintptr_t>(a.ctab));
+  constexpr uint32_t SKEW_NEG = 0xBC00BC00u;
+  uint32_t skew_c0 = 0;  // c of this wave's row 0 in column -1 (frame wave R - 1)
+  if constexpr (SKEW) skew_c0 = ct[wave * R + 1];
+  // a tile's column -1: H = 0 in every row's frame (Hl[r] = c_{wave R + r - 1}), the diagonal
+  // above it, and the running best in the frame its first column's first step starts from
+  const auto skew_reset = [&](u16x2 (&H)[R], u16x2 (&X)[R], u16x2& bst, u16x2& pup) {
+    // (from an opaque copy: the 2R values are loop-invariant, and LLVM would otherwise keep
+    // them live across the column loop, R VGPRs spilled)
+    uint32_t c0 = skew_c0;
+    asm volatile("" : "+v"(c0));
+    f16x2 h = as_f16x2(__builtin_bit_cast(u16x2, c0));
+    const f16x2 ne = as_f16x2(as_u16x2(a.f16_ne));
+    pup = as_u16x2(h + ne);
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      H[r] = as_u16x2(h);
+      X[r] = __builtin_bit_cast(u16x2, SKEW_NEG);
+      h = h - ne;
+    }
+    bst = H[R - 2];
+  };
+  (void)ct; (void)skew_reset;
   if (wave == 0) {
     // (entry 64 of the first ring slot's C rows: no lane's own entry, so no wave overwrites it)
     if (lane < C)
@@ -245,6 +287,7 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
   }
   u16x2 best = {0, 0};
   u16x2 prevUpH = H0;  // H(row above, column -1)
+  if constexpr (SKEW) skew_reset(Hl, Xl, best, prevUpH);
   uint2 rlo, rhi;      // raw codes of the next chunk (prefetched one phase ahead)
   load_raw<C, !MQ>(cur, vc0, vc0 < nfull, a.pad, packed, rlo, rhi);
   if (STREAM && threadIdx.x == 0) sq[W] = total;
@@ -457,6 +500,23 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
       uint2* rout = wave < W - 1 ? ring + ((size_t)(wave * 2 + slot) * C) * RS + lane
                     : W > 1      ? rin
                                  : ring + lane;
+      // SKEW: the floors of this chunk-phase's frames, cs[s] = c_k for k = wave R + 8 c - 1 + s
+      // (row r of column jj: s = r + jj + 1), wave-uniform, read into SGPRs.  Wave 0 has no wave
+      // above it: its row -1 holds H = 0 in a frame that moves with the column, so it rewrites
+      // the boundary entries of the 8 column rows before it reads them (the same wave's LDS
+      // accesses stay in order)
+      const int cu = __builtin_amdgcn_readfirstlane(c);
+      uint32_t cs[SKEW ? R + C : 1];
+      if constexpr (SKEW) {
+        cst_u32* const sl = ct + (wave * R + cu * C + 1);
+#pragma unroll
+        for (int s = 0; s < R + C; ++s) cs[s] = sl[s];
+        if (wave == 0 && lane == 0) {
+#pragma unroll
+          for (int jj = 0; jj < C; ++jj) ring[jj * RS + 64] = make_uint2(cs[jj], SKEW_NEG);
+        }
+      }
+      (void)cu; (void)cs;
       uint2 rv = rin[0];
       ProfLookup16<PROF && F16 ? R : 2> lkq;  // f16 profile: the next column's words
       (void)lkq;
@@ -531,6 +591,62 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
           } else {
             column_merged<R, RB, false>(lk, diag, upX, Hl, Xl, best, S2, O2, E2);
           }
+        } else if constexpr (PAIR && SKEW) {
+          // the skewed rows (scripts/gen_f16_rows.py, skew_pair_block): 5 VALU per row; the
+          // table words hold s + 2e, row r's floor is cs[r + jj + 1]
+          const uint32_t nwl = jj + 1 < C ? (jj + 1 < 4 ? clo.x : clo.y) : rlo.x;
+          const uint32_t nwh = jj + 1 < C ? (jj + 1 < 4 ? chi.x : chi.y) : rhi.x;
+          const int nsh = jj + 1 < C ? 8 * ((jj + 1) & 3) : 0;
+          uint32_t Da, Db, AO;
+          const uint32_t no = as_u32(as_u16x2(NO2)), e2 = a.f16_e2, e2f = a.f16_e2f;
+          u16x2 bst = best;
+#define SWK_SKEW_OUT(B, DA)                                                                   \
+  [h0] "+v"(Hl[B]), [h1] "+v"(Hl[B + 1]), [h2] "+v"(Hl[B + 2]), [h3] "+v"(Hl[B + 3]),          \
+      [h4] "+v"(Hl[B + 4]), [h5] "+v"(Hl[B + 5]), [h6] "+v"(Hl[B + 6]), [h7] "+v"(Hl[B + 7]),  \
+      [t0] "+v"(Xl[B]), [t1] "+v"(Xl[B + 1]), [t2] "+v"(Xl[B + 2]), [t3] "+v"(Xl[B + 3]),      \
+      [t4] "+v"(Xl[B + 4]), [t5] "+v"(Xl[B + 5]), [t6] "+v"(Xl[B + 6]), [t7] "+v"(Xl[B + 7]),  \
+      [Db] "=&v"(Db), [best] "+v"(bst), [Da] DA(Da), [AO] DA(AO)
+#define SWK_SKEW_IN(B, P0, P1)                                                                \
+  [p0] "v"(P0.x), [p1] "v"(P0.y), [p2] "v"(P0.z), [p3] "v"(P0.w), [p4] "v"(P1.x),             \
+      [p5] "v"(P1.y), [p6] "v"(P1.z), [p7] "v"(P1.w), [no] "s"(no), [e2] "s"(e2),             \
+      [c0] "s"(cs[B + jj + 1]), [c1] "s"(cs[B + jj + 2]), [c2] "s"(cs[B + jj + 3]),           \
+      [c3] "s"(cs[B + jj + 4]), [c4] "s"(cs[B + jj + 5]), [c5] "s"(cs[B + jj + 6]),           \
+      [c6] "s"(cs[B + jj + 7]), [c7] "s"(cs[B + jj + 8])
+#define SWK_SKEW_BLOCK(KIND, B, P0, P1)                                                       \
+  if constexpr (KIND == 0)                                                                    \
+    asm volatile(SWK_F16SKEW_F : SWK_SKEW_OUT(B, "=&v")                                       \
+                 : SWK_SKEW_IN(B, P0, P1), [e2f] "s"(e2f), [up] "v"(upX), [dg] "v"(diag),     \
+                   [pw] "v"(pw));                                                             \
+  else if constexpr (KIND == 1)                                                               \
+    asm volatile(SWK_F16SKEW_M : SWK_SKEW_OUT(B, "+v") : SWK_SKEW_IN(B, P0, P1),              \
+                 [up] "v"(Xl[B - 1]));                                                        \
+  else                                                                                        \
+    asm volatile(SWK_F16SKEW_L : SWK_SKEW_OUT(B, "+v") : SWK_SKEW_IN(B, P0, P1),              \
+                 [up] "v"(Xl[B - 1]));
+          // (the table words one block ahead, as in the unskewed column below)
+          uint4 pB0 = ld4(acur + 48), pB1 = ld4(acur + 64);  // block 1
+          __builtin_amdgcn_sched_barrier(0);
+          SWK_SKEW_BLOCK(0, 0, pA0, pA1)
+          pA0 = ld4(acur + 80);  // block 2
+          pA1 = ld4(acur + 96);
+          __builtin_amdgcn_sched_barrier(0);
+          SWK_SKEW_BLOCK(1, 8, pB0, pB1)
+          pB0 = ld4(acur + 112);  // block 3
+          pB1 = ld4(acur + 128);
+          __builtin_amdgcn_sched_barrier(0);
+          SWK_SKEW_BLOCK(1, 16, pA0, pA1)
+          acur = pair_addr(nwl, nwh, nsh);  // next column: block 0 and row-0 word
+          pA0 = ld4(acur + 16);
+          pA1 = ld4(acur + 32);
+          pw = ld1(acur + 12);
+          __builtin_amdgcn_sched_barrier(0);
+          SWK_SKEW_BLOCK(2, R - 8, pB0, pB1)
+#undef SWK_SKEW_BLOCK
+#undef SWK_SKEW_OUT
+#undef SWK_SKEW_IN
+          (void)Db; (void)AO;
+          best = bst;
+          upX = Xl[R - 1];
         } else if constexpr (PAIR) {
           // the next column's table address (its codes: this chunk, or byte 0 of the next)
           const uint32_t nwl = jj + 1 < C ? (jj + 1 < 4 ? clo.x : clo.y) : rlo.x;
@@ -650,14 +766,34 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
         if (BAL && k == 0 && bf > 0) {  // BAL: a head visit ends: hand its state over
           bal_store((int)blockIdx.x + 1);
         } else {  // this wave's part of tile k is done
+        if constexpr (SKEW) {
+          // the odd rows of the tile's last column (no later column pairs them), then out of
+          // the frame the best ends in: that of this wave's last row in the last column
+          f16x2 bb = as_f16x2(best);
+          const f16x2 e2 = as_f16x2(as_u16x2(a.f16_e2)), e2f = as_f16x2(as_u16x2(a.f16_e2f));
+#pragma unroll
+          for (int r = 1; r < R; r += 2) bb = fmax2(bb + (r == 1 ? e2f : e2), as_f16x2(Hl[r]));
+          const uint32_t cf =
+              ct[__builtin_amdgcn_readfirstlane(wave * R + R + 1 + cu * C + ncols - 1)];
+          best = as_u16x2(bb - as_f16x2(__builtin_bit_cast(u16x2, cf)));
+        }
         uint32_t* bs = bestsh + (k % W) * SWB_TILE;
-        atomicMax(&bs[lane], (uint32_t)best.x);
-        atomicMax(&bs[lane + 64], (uint32_t)best.y);
+        if constexpr (SKEW) {
+          // (from an opaque copy of the lane: the address is loop-invariant, and the skewed
+          // column has no VGPR to hold it)
+          uint32_t ol = (uint32_t)lane;
+          asm volatile("" : "+v"(ol));
+          bs += ol;
+        } else {
+          bs += lane;
+        }
+        atomicMax(&bs[0], (uint32_t)best.x);
+        atomicMax(&bs[64], (uint32_t)best.y);
         if (wave == W - 1) {  // every other wave folded tile k in an earlier phase
           const size_t tlo = (size_t)tile * SWB_TILE + lane, thi = tlo + 64;
-          int32_t blo = (int32_t)bs[lane], bhi = (int32_t)bs[lane + 64];
-          bs[lane] = 0;
-          bs[lane + 64] = 0;
+          int32_t blo = (int32_t)bs[0], bhi = (int32_t)bs[64];
+          bs[0] = 0;
+          bs[64] = 0;
           if constexpr (F16) {  // f16 bit patterns of non-negative integers -> int
             blo = f16_unscore((uint32_t)blo);
             bhi = f16_unscore((uint32_t)bhi);
@@ -688,6 +824,7 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
         }
         best = (u16x2){0, 0};
         prevUpH = H0;
+        if constexpr (SKEW) skew_reset(Hl, Xl, best, prevUpH);
         tile = ntile;
         if constexpr (STREAM) {
           packed = packed_n;
@@ -767,13 +904,14 @@ static size_t tile_ring_entries(int W, int C, bool seg_in) {
 }
 
 template <int R, int RB, bool COL0, bool PROF, bool GOTOH, bool F16, bool PAIR = false,
-          bool MQ = false, bool STREAM = false, int C = 8, bool BAL = false, bool TRIM = false>
+          bool MQ = false, bool STREAM = false, int C = 8, bool BAL = false, bool TRIM = false,
+          bool SKEW = false>
 static hipError_t launch_score(const ScoreArgs& a, int W, uint32_t prof_bytes, hipStream_t st,
                                unsigned bal_grid = 0) {
   const size_t ntiles = (a.n + SWB_TILE - 1) / SWB_TILE * (MQ ? a.nq : 1);  // units
   const size_t lds = (size_t)W * SWB_TILE * 4 + tile_ring_entries(W, C, a.edge_in != nullptr) * 8 +
                      (PROF ? prof_bytes : 0) + (PAIR ? a.PS : 0) + (STREAM ? 256 : 0);
-  auto fn = &score_kernel<R, RB, COL0, PROF, GOTOH, F16, PAIR, MQ, STREAM, C, BAL, TRIM>;
+  auto fn = &score_kernel<R, RB, COL0, PROF, GOTOH, F16, PAIR, MQ, STREAM, C, BAL, TRIM, SKEW>;
   static bool attr_set = false;
   if (!attr_set) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn),
@@ -796,6 +934,13 @@ static hipError_t launch_score(const ScoreArgs& a, int W, uint32_t prof_bytes, h
   if (BAL && (grid == 0 || ntiles < 2 * (size_t)grid)) return hipErrorInvalidConfiguration;
   hipLaunchKernelGGL(fn, dim3(grid), dim3(64 * W), (unsigned)lds, st, a);
   return hipGetLastError();
+}
+
+// The SKEW variants' arguments: the floor table and the running best's two frame steps.
+static void skew_args(ScoreArgs& a, const uint32_t* tab, int R) {
+  a.ctab = tab;
+  a.f16_e2 = f16_pair(2 * (int)a.E);
+  a.f16_e2f = f16_pair((3 - R) * (int)a.E);
 }
 
 }  // namespace swk
@@ -833,7 +978,7 @@ extern "C" hipError_t swk_launch_score(int R, int RB, int col0, int prof, int go
                                        const uint32_t* ident, int pair, uint32_t pS1,
                                        uint32_t pS2, uint32_t ulen, uint32_t ustride,
                                        uint32_t nq, uint32_t qwords, size_t sstride,
-                                       hipStream_t st) {
+                                       hipStream_t st, const uint32_t* skew_tab) {
   if (n == 0) return hipSuccess;
   swk::ScoreArgs a{res,  offs, lens, n,  qtab, nv, S,
                    O,    E,    PS,   pad, scores, static_cast<const uint2*>(edge_in),
@@ -867,6 +1012,14 @@ extern "C" hipError_t swk_launch_score(int R, int RB, int col0, int prof, int go
     return hipErrorInvalidValue;
   }
   if (pair) {  // PS = pair-table bytes
+    // skew_tab: the skewed rows (qtab holds s + 2e, skew_tab the frames' floors); one segment
+    if (skew_tab && (R != 32 || !f16 || prof || gotoh || col0 || edge_in || edge_out || W > 4))
+      return hipErrorInvalidValue;
+    if (skew_tab) {
+      swk::skew_args(a, skew_tab, 32);
+      return swk::launch_score<32, 4, false, false, false, true, true, false, false, 8, false,
+                               false, true>(a, W, 0, st);
+    }
     if (R == 32 && f16 && !prof && !gotoh && !col0)
       return swk::launch_score<32, 4, false, false, false, true, true>(a, W, 0, st);
     // DNA Gotoh: 8-column chunks while the hand-off ring fits beside the table, else 4 (a
@@ -928,9 +1081,15 @@ extern "C" hipError_t swk_bal_plan_uniform(void* plan, uint32_t ntiles, uint32_t
   return hipGetLastError();
 }
 
-extern "C" unsigned swk_bal_slots(int W, uint32_t PS, int trim) {
+extern "C" unsigned swk_bal_slots(int W, uint32_t PS, int trim, int skew) {
   const void* fn =
-      trim ? reinterpret_cast<const void*>(
+      skew ? (trim ? reinterpret_cast<const void*>(
+                         &swk::score_kernel<32, 4, false, false, false, true, true, false, false,
+                                            8, true, true, true>)
+                   : reinterpret_cast<const void*>(
+                         &swk::score_kernel<32, 4, false, false, false, true, true, false, false,
+                                            8, true, false, true>))
+      : trim ? reinterpret_cast<const void*>(
                  &swk::score_kernel<32, 4, false, false, false, true, true, false, false, 8, true,
                                     true>)
            : reinterpret_cast<const void*>(
@@ -955,7 +1114,8 @@ extern "C" hipError_t swk_launch_pair_bal(const uint8_t* res, const uint64_t* of
                                           const uint32_t* nidx, const uint32_t* ident,
                                           const void* plan, uint32_t* fault, uint32_t poll_limit,
                                           uint32_t stall, int trim, uint32_t packed,
-                                          const uint32_t* sidx, hipStream_t st) {
+                                          const uint32_t* sidx, hipStream_t st,
+                                          const uint32_t* skew_tab) {
   if (n == 0) return hipSuccess;
   if (W > 4 || !flag || !state || !plan || !fault || poll_limit == 0 || (idx && !nidx) ||
       (packed != SWK_PACK_BYTES && packed != SWK_PACK_NIBBLE) || (sidx && (!trim || idx)))
@@ -976,6 +1136,14 @@ extern "C" hipError_t swk_launch_pair_bal(const uint8_t* res, const uint64_t* of
   a.poll_limit = poll_limit;
   a.stall = stall;
   a.sidx = sidx;
+  if (skew_tab) {  // the skewed rows (qtab holds s + 2e)
+    swk::skew_args(a, skew_tab, 32);
+    if (trim)
+      return swk::launch_score<32, 4, false, false, false, true, true, false, false, 8, true, true,
+                               true>(a, W, 0, st, grid);
+    return swk::launch_score<32, 4, false, false, false, true, true, false, false, 8, true, false,
+                             true>(a, W, 0, st, grid);
+  }
   if (trim)  // (a ragged batch: its tiles' last chunks stop at their last column)
     return swk::launch_score<32, 4, false, false, false, true, true, false, false, 8, true, true>(
         a, W, 0, st, grid);

@@ -138,6 +138,23 @@ sw_status launch(sw_bank* b, const uint8_t* d_res, const uint64_t* d_offs,
   const char* arith = opt16 ? "f16+u16-rescore" : use_f16 ? "f16" : "u16";
   // the f16 pass of the tile kernel reads the letter-pair table when the query has one
   const bool use_pair = use_f16 && b->pair_bytes != 0 && env_int("SWBANK_PAIR", 1) != 0;
+  // The skewed rows of the merged pair kernel (DESIGN 3.1, 5 VALU per row instead of 5.5):
+  // every cell carries its anti-diagonal's offset e (k - 1), k < rows + cols, on top of its
+  // value, so the exact range must hold both: max(s) min(|q|, L) + max(s) + e (rows + cols) <=
+  // 2048 and the most negative intermediate >= -2048.  rows: the workgroup's (the query padded
+  // to whole waves); cols: the columns a tile runs, max_len rounded up to the 8-column chunk
+  // (only the trimmed kernel stops at a tile's last code: the frames, the running best and the
+  // unshift of the others go on through the last chunk's padding).  Past that bound nothing
+  // changes (the skewed rows have no optimistic mode).  One query segment, batches resident in
+  // byte or 4-bit codes through the device API (the host feeder's chunk launches, records and
+  // mixed chunks keep the unskewed rows); SWBANK_SKEW=0 keeps them everywhere (A/B).
+  const uint64_t skew_cols = ((uint64_t)max_len + 7) / 8 * 8;
+  const bool skew =
+      exact16 && use_pair && !gotoh && nseg == 1 && b->skew_entries != 0 && wait_prev &&
+      (packed == SWK_PACK_BYTES || packed == SWK_PACK_NIBBLE) &&
+      top + (uint64_t)b->E * ((uint64_t)b->segs[0].W * b->R + skew_cols) <= 2048u &&
+      b->skew_neg >= -2048 && skew_cols + 136 <= b->skew_entries &&
+      env_int("SWBANK_SKEW", 1) != 0;
   bool wave_fb = false;  // the wave kernel re-scores its own flagged pairs
   if (use_wave) {
     // f16 profile, one segment of <= 512 rows (configs[4]): two pairs per wave, 16 rows per
@@ -291,8 +308,10 @@ sw_status launch(sw_bank* b, const uint8_t* d_res, const uint64_t* d_offs,
   } else {
     int R0 = b->R, W0 = b->segs[0].W;  // (the first pass's rows per wave)
     u16_gotoh_rows(b, use_f16, R0, W0);
-    snprintf(b->last_kernel, sizeof(b->last_kernel), "tile %s%s R=%d W=%d segs=%zu", arith,
-             b->prof ? "-profile" : use_pair ? " pair" : "", R0, W0, nseg);
+    // (" skew" follows the layout tokens: the tokens of the launch kind, " balanced grid=N"
+    // among them, stay last)
+    snprintf(b->last_kernel, sizeof(b->last_kernel), "tile %s%s R=%d W=%d segs=%zu%s", arith,
+             b->prof ? "-profile" : use_pair ? " pair" : "", R0, W0, nseg, skew ? " skew" : "");
   }
   // A device batch (dsort) visits its targets longest first, sorted on the device, so every
   // tile holds similar lengths (a tile runs to its longest lane); SWBANK_DSORT=0 disables.
@@ -308,7 +327,7 @@ sw_status launch(sw_bank* b, const uint8_t* d_res, const uint64_t* d_offs,
       b->R == 32 && b->segs[0].W <= 4 && n <= 0xFFFFFFFFull && env_int("SWBANK_DSORT", 1) != 0 &&
       env_int("SWBANK_BAL", 1) != 0 && env_int("SWBANK_BAL_RAGGED", 1) != 0 &&
       !one_len_bin(min_len, max_len)) {
-    const unsigned grid = swk_bal_slots(b->segs[0].W, b->pair_bytes, ragged_trim());
+    const unsigned grid = swk_bal_slots(b->segs[0].W, b->pair_bytes, ragged_trim(), skew ? 1 : 0);
     const size_t kmin = std::max<uint32_t>(1u, (min_len + 7) / 8), kmax = (max_len + 7) / 8;
     if (grid && ntiles * kmin >= 2 * (size_t)grid * kmax && ntiles * kmax < (1ull << 31))
       rbal_grid = grid;
@@ -407,7 +426,8 @@ sw_status launch(sw_bank* b, const uint8_t* d_res, const uint64_t* d_offs,
                    ntiles * ((max_len + 7) / 8) < (1ull << 31) && !opt16 && b->R == 32 &&
                    b->segs[0].W <= 4 && env_int("SWBANK_BAL", 1) != 0)) {
         const int Wl = b->segs[0].W;
-        const unsigned grid = rbal ? rbal_grid : swk_bal_slots(Wl, b->pair_bytes, 0);
+        const unsigned grid = rbal ? rbal_grid
+                                   : swk_bal_slots(Wl, b->pair_bytes, 0, skew ? 1 : 0);
         uint32_t* fw = fault_word(b);
         if (!fw) return fail(b, SW_ERR_NOMEM, "fault word allocation failed");
         if (grid && (rbal || ntiles >= 2 * (size_t)grid)) {
@@ -454,7 +474,8 @@ sw_status launch(sw_bank* b, const uint8_t* d_res, const uint64_t* d_offs,
             HIPOK(b, swk_deal_gather(res, offs, lens, idx, ident, n, &dl, st));
           }
           HIPOK(b, swk_launch_pair_bal(gat ? b->gres.p : res, gat ? b->goffs.p : offs,
-                                       gat ? b->glens.p : lens, np, b->qpair.p, b->nv16, b->S, b->O,
+                                       gat ? b->glens.p : lens, np,
+                                       skew ? b->qpair_skew.p : b->qpair.p, b->nv16, b->S, b->O,
                                        b->E, b->pair_bytes, b->pad, Wl,
                                        scores, b->pS1, b->pS2, ulen,
                                        ustride, b->bal_flag.p, b->bal_state.p, ++b->bal_gen, grid,
@@ -465,7 +486,8 @@ sw_status launch(sw_bank* b, const uint8_t* d_res, const uint64_t* d_offs,
                                        rbal && ragged_trim(),
                                        gnib ? (uint32_t)SWK_PACK_NIBBLE
                                             : gat ? (uint32_t)SWK_PACK_BYTES : packed,
-                                       gat ? idx : nullptr, st));
+                                       gat ? idx : nullptr, st,
+                                       skew ? b->skew_ctab.p : nullptr));
           ++b->ctr.balanced_calls;
           const size_t L = strlen(b->last_kernel);
           snprintf(b->last_kernel + L, sizeof(b->last_kernel) - L, " balanced grid=%u%s", grid,
@@ -481,7 +503,8 @@ sw_status launch(sw_bank* b, const uint8_t* d_res, const uint64_t* d_offs,
         u16_gotoh_rows(b, f16, R, Wl);
         HIPOK(b, swk_launch_score(R, b->RB, b->col0, b->prof, gotoh ? 1 : 0, f16 ? 1 : 0, res,
                                   offs, lens, np,
-                                  pair ? b->qpair.p + s * (b->pair_bytes / 4)
+                                  pair && skew ? b->qpair_skew.p
+                                  : pair       ? b->qpair.p + s * (b->pair_bytes / 4)
                                   : f16 ? b->qtab16.p + b->segs[s].off16
                                         : b->qtab.p + b->segs[s].off,
                                   f16 ? b->nv16 : b->nv, b->S, b->O, b->E,
@@ -489,7 +512,8 @@ sw_status launch(sw_bank* b, const uint8_t* d_res, const uint64_t* d_offs,
                                   b->pad, Wl, scores, ein, eout, ecols, s > 0 ? 1 : 0,
                                   (int)packed, idx, nidx, (uint32_t)p0,
                                   pass == 0 ? ident : nullptr, pair ? 1 : 0, b->pS1, b->pS2,
-                                  ulen, ustride, 1u, 0u, 0, st));
+                                  ulen, ustride, 1u, 0u, 0, st,
+                                  pair && skew ? b->skew_ctab.p : nullptr));
       }
     }
   }
