@@ -40,9 +40,6 @@
 
 #include "swbank_internal.h"
 
-#ifndef SWK_TAIL_TOP
-#define SWK_TAIL_TOP 1
-#endif
 #ifndef SWK_PRIO_ROT
 // Rotating wave priorities in the persistent tile kernel: the SIMD issues from the oldest ready
 // wave first, so of the 4 resident workgroups of a CU the first dispatched ran ahead and
@@ -247,9 +244,6 @@ __device__ __forceinline__ void column_gotoh_f16(const LK& lk, u16x2& diag_, u16
 #ifndef SWK_F16_ASM
 #define SWK_F16_ASM 1
 #endif
-#ifndef SWK_F16_COLBLOCK
-#define SWK_F16_COLBLOCK 1
-#endif
 #include "swbank_f16_rows.inc"
 #define SWK_F16_HT(B)                                                                         \
   [h0] "+v"(Hl[B]), [h1] "+v"(Hl[B + 1]), [h2] "+v"(Hl[B + 2]), [h3] "+v"(Hl[B + 3]),          \
@@ -294,7 +288,6 @@ __device__ __forceinline__ void column_f16_asm(const LK& lk, u16x2& diag_, u16x2
   constexpr bool PROF = !std::is_same<LK, LutLookup<R>>::value;
   uint32_t Da, Db, S1, X, DN, IN;
   u16x2 best = best_, up = upX_;
-#if SWK_F16_COLBLOCK
   if constexpr ((R == 32 || R == 16) && !GOTOH && !PROF && !ZDOWN) {
     // DNA LUT merged (the headline): the whole column (prologue + R rows) as one asm block
 #define SWK_F16_COLASM(RR)                                                                    \
@@ -313,7 +306,6 @@ __device__ __forceinline__ void column_f16_asm(const LK& lk, u16x2& diag_, u16x2
     best_ = best;
     return;
   }
-#endif
   if constexpr (PROF)
     asm volatile(
         "v_perm_b32 %[Da], %[h0], %[l0], %[sA]\n\t"
@@ -880,9 +872,6 @@ __device__ __forceinline__ int tile_nch(const uint8_t* res, const uint32_t* lens
 #ifndef SWK_STREAM_POLL
 #define SWK_STREAM_POLL 64  // streamed batches: waits between one workgroup's host-word reads
 #endif
-#ifndef SWK_STREAM_POLL_ALL
-#define SWK_STREAM_POLL_ALL 0  // 1: every wave reads the host word (round-5 form)
-#endif
 __device__ __forceinline__ uint32_t stream_mode(const uint32_t* hflag, uint32_t* dflag, int c,
                                                 int nsc, int lane) {
   for (int it = 0; it < (1 << 20); ++it) {
@@ -897,11 +886,10 @@ __device__ __forceinline__ uint32_t stream_mode(const uint32_t* hflag, uint32_t*
     }
     // The host word is read over PCIe: by each workgroup's first wave only (the others follow
     // the device word it sets), on arrival and then every SWK_STREAM_POLL-th wait, staggered over
-    // the workgroups.  Every waiting wave reading it every 16th wait (the round-5 form,
-    // SWK_STREAM_POLL_ALL=1 SWK_STREAM_POLL=16: ~600 PCIe reads a microsecond across the chip
-    // while the first chunks cross) made host calls on the headline batch 2.3-2.6 ms instead of
-    // 1.9-2.05 (same box, alternating).
-    if ((SWK_STREAM_POLL_ALL || threadIdx.x < 64) &&
+    // the workgroups.  Every waiting wave reading it every 16th wait (the round-5 form: ~600
+    // PCIe reads a microsecond across the chip while the first chunks cross) made host calls on
+    // the headline batch 2.3-2.6 ms instead of 1.9-2.05 (same box, alternating).
+    if (threadIdx.x < 64 &&
         (it == 0 || ((it + (int)blockIdx.x) % SWK_STREAM_POLL) == 0)) {
       v = __builtin_amdgcn_readfirstlane(
           __hip_atomic_load(hflag + c, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM));

@@ -93,40 +93,6 @@ __device__ __forceinline__ void column_merged_f16_mask(const LK& lk, u16x2& diag
 // generated row blocks as the tile kernel with the lane's own LUT words / profile words in
 // VGPRs.  K = 4: one 4-row block; K = 8, 16: 8-row blocks.
 #define SWK_CLAMP(x, n) ((x) < (n) ? (x) : (n) - 1)
-#ifndef SWK_RING_PF
-#define SWK_RING_PF 1  // wave kernel, f16 profile: read the code ring one step ahead
-#endif
-#ifndef SWK_HALF_UNROLL
-#define SWK_HALF_UNROLL 4  // two-pairs wave kernel: steps per loop iteration (2 or 4)
-#endif
-#ifndef SWK_HALF_AHEAD
-#define SWK_HALF_AHEAD 1  // two-pairs wave kernel: profile words one step ahead
-#endif
-#ifndef SWK_HALF_DPPSEL
-// two-pairs wave kernel: the row above moves down and each half's lane 0 takes the row -1
-// boundary in ONE v_cndmask_b32_dpp per value (the shift as the select's DPP operand, the
-// boundary lanes in VCC) instead of a DPP move and a v_cndmask
-#define SWK_HALF_DPPSEL 1
-#endif
-#ifndef SWK_HALF_FMA
-// two-pairs wave kernel: LDS profile words {s, 1.0} (4 B per letter and row) added with one
-// op_sel FMA per row (gen_f16_rows.py mode F) instead of 2-byte entries interleaved by a v_perm
-#define SWK_HALF_FMA 1
-#endif
-#ifndef SWK_HALF_ABSRING
-// two-pairs wave kernel (FMA profile, words a step ahead): the code ring holds each lane's
-// profile ADDRESS (relative to the ring slot), so with the 32-step ring window unrolled no step
-// computes an LDS address: no profile-address add, no ring-pointer op (wave_two_pairs)
-#define SWK_HALF_ABSRING 1
-#endif
-// the two-pairs kernel's LDS: the profile (letter stride SWK_HALF_LS bytes, 512 rows) and
-// each wave's code ring (profile offsets of both halves' targets, SWK_HALF_RING bytes a wave);
-// SWK_HALF_ABSRING: wave 0's ring first, the profile at byte SWK_HALF_ABS_BASE, the other
-// waves' rings after it (the same total)
-#define SWK_HALF_LS (SWK_HALF_FMA ? 2048u : 1024u)
-#define SWK_HALF_RING (SWK_HALF_FMA ? 512u : 1024u)
-#define SWK_HALF_ABS (SWK_HALF_ABSRING && SWK_HALF_FMA && SWK_HALF_AHEAD)
-#define SWK_HALF_ABS_BASE 512u
 #define SWK_W_HT(B)                                                                           \
   [h0] "+v"(Hl[B]), [h1] "+v"(Hl[SWK_CLAMP(B + 1, K)]), [h2] "+v"(Hl[SWK_CLAMP(B + 2, K)]),    \
       [h3] "+v"(Hl[SWK_CLAMP(B + 3, K)]), [h4] "+v"(Hl[SWK_CLAMP(B + 4, K)]),                  \
@@ -271,6 +237,40 @@ __device__ __forceinline__ __attribute__((address_space(1))) T* global_ptr(T* p)
   return (__attribute__((address_space(1))) T*)p;
 }
 
+// Length of target t: a CAPI record's own field (clamped), the batch's uniform length, or lens[t].
+__device__ __forceinline__ uint32_t target_len(const ScoreArgs& a, size_t t) {
+  return a.packed == SWK_PACK_RECORDS ? record_len(a.res + t * SWB_RECORD)
+         : a.ustride                  ? a.ulen
+                                      : a.lens[t];
+}
+
+// The two targets of a pair: lengths and code pointers of the caller's pointer kind (generic, or
+// address space 1 through global_ptr).  The callers fill it themselves: wave_pair selects target
+// B's index inside each pointer branch and wave_two_pairs before them, and one shared form
+// changes the instruction stream of one or the other.  (wave_tail_seg keeps its own copy of the
+// length rule and of the code read for the same reason.)
+template <class Ptr>
+struct PairTargets {
+  uint32_t LA, LB;
+  Ptr pA, pB;
+  // the letters of column c of both targets: bytes, 2-bit (packed) or 4-bit (nib) codes, pad
+  // past the end
+  __device__ __forceinline__ uint2 codes(uint32_t c, bool nib, bool packed, uint32_t pad) const {
+    uint32_t x = pad, y = pad;
+    if (nib) {
+      if (c < LA) x = (pA[c >> 1] >> (4 * (c & 1))) & 15u;
+      if (c < LB) y = (pB[c >> 1] >> (4 * (c & 1))) & 15u;
+    } else if (packed) {
+      if (c < LA) x = (pA[c >> 2] >> (2 * (c & 3))) & 3u;
+      if (c < LB) y = (pB[c >> 2] >> (2 * (c & 3))) & 3u;
+    } else {
+      if (c < LA) x = pA[c];
+      if (c < LB) y = pB[c];
+    }
+    return make_uint2(min(x, pad), min(y, pad));
+  }
+};
+
 // wave_pair's loop flavours: row -1 from a previous segment (in), bottom row written (out)
 template <bool I, bool O>
 struct SegT {
@@ -307,24 +307,20 @@ __device__ __forceinline__ uint2 wave_pair(const ScoreArgs& a, const uint8_t* pr
                                            uint2* lout = nullptr, int nph = 0, int seg = 0,
                                            int P = 1, uint8_t* cring = nullptr) {
   constexpr bool RING = F16 && PROF && !SPLIT;
-  constexpr bool PF = SWK_RING_PF != 0;  // ring letters read one step ahead
   const size_t tA = 2 * pair, tB = tA + 1;
   const size_t n = a.n;
   const bool packed = a.packed != SWK_PACK_BYTES, rec = a.packed == SWK_PACK_RECORDS;
   const bool nib = a.packed == SWK_PACK_NIBBLE;
   const bool uni = a.ustride != 0;
-  const uint32_t LA = rec ? record_len(a.res + tA * SWB_RECORD) : uni ? a.ulen : a.lens[tA];
-  const uint32_t LB = tB >= n ? 0u
-                      : rec ? record_len(a.res + tB * SWB_RECORD)
-                      : uni ? a.ulen
-                            : a.lens[tB];
+  const uint32_t LA = target_len(a, tA), LB = tB >= n ? 0u : target_len(a, tB);
   const auto pA = global_ptr(rec ? a.res + tA * SWB_RECORD + 6
                                   : uni ? a.res + tA * a.ustride
                                         : a.res + (LA ? a.offs[tA] : 0));
   const auto pB = global_ptr(rec ? a.res + (tB < n ? tB : tA) * SWB_RECORD + 6
                                   : uni ? a.res + (tB < n ? tB : tA) * a.ustride
                                         : a.res + (LB ? a.offs[tB] : 0));
-  const int Lmax = (int)__builtin_amdgcn_readfirstlane(max(LA, LB));
+  const PairTargets<decltype(global_ptr(a.res))> tg{LA, LB, pA, pB};
+  const int Lmax = (int)__builtin_amdgcn_readfirstlane(max(tg.LA, tg.LB));
   const uint32_t S = a.S, pad = a.pad;
   const u16x2 S2 = {(unsigned short)S, (unsigned short)S};
   const u16x2 O2 = {(unsigned short)a.O, (unsigned short)a.O};
@@ -385,19 +381,9 @@ __device__ __forceinline__ uint2 wave_pair(const ScoreArgs& a, const uint8_t* pr
   // the codes of column c of both targets (pad past the end): RING as {A, B << 8}, else the
   // code word
   const auto load_codes = [&](const uint32_t c) __attribute__((always_inline)) -> uint32_t {
-    uint32_t x = pad, y = pad;
-    if (nib) {
-      if (c < LA) x = (pA[c >> 1] >> (4 * (c & 1))) & 15u;
-      if (c < LB) y = (pB[c >> 1] >> (4 * (c & 1))) & 15u;
-    } else if (packed) {
-      if (c < LA) x = (pA[c >> 2] >> (2 * (c & 3))) & 3u;
-      if (c < LB) y = (pB[c >> 2] >> (2 * (c & 3))) & 3u;
-    } else {
-      if (c < LA) x = pA[c];
-      if (c < LB) y = pB[c];
-    }
-    if constexpr (RING) return min(x, pad) | (min(y, pad) << 8);
-    else return code_word(min(x, pad), min(y, pad));
+    const uint2 l = tg.codes(c, nib, packed, pad);
+    if constexpr (RING) return l.x | (l.y << 8);
+    else return code_word(l.x, l.y);
   };
   const auto ring_write = [&](const uint32_t nc) __attribute__((always_inline)) {
     cring[lane] = (uint8_t)ringprev;  // letters of target A at [0, 128), B at [128, 256)
@@ -406,10 +392,11 @@ __device__ __forceinline__ uint2 wave_pair(const ScoreArgs& a, const uint8_t* pr
     cring[192 + lane] = (uint8_t)(nc >> 8);
     ringprev = nc;
   };
-  uint32_t nra = 0, nrb = 0;  // RING && PF: the letters of the next step's column
-  // RING && PF: this lane's ring position of step 0 (step T + j reads ring byte 64 + j - lane)
-  const uint8_t* const cring_l = RING && PF ? cring + 64 - lane : nullptr;
-  if constexpr (RING && PF) {
+  // RING: the ring is read one step ahead
+  uint32_t nra = 0, nrb = 0;  // the letters of the next step's column
+  // this lane's ring position of step 0 (step T + j reads ring byte 64 + j - lane)
+  const uint8_t* const cring_l = RING ? cring + 64 - lane : nullptr;
+  if constexpr (RING) {
     ring_write(load_codes((uint32_t)lane));
     nra = cring_l[0];
     nrb = cring_l[128];
@@ -422,12 +409,11 @@ __device__ __forceinline__ uint2 wave_pair(const ScoreArgs& a, const uint8_t* pr
     constexpr bool SEGO = decltype(segc)::out;
     if (even && (t & 63) == 0) {  // next 64 columns, one code pair per lane
       const uint32_t c = (uint32_t)t + lane;
-      if constexpr (RING && !PF) ring_write(load_codes(c));
-      else if constexpr (!RING) buf = load_codes(c);
+      if constexpr (!RING) buf = load_codes(c);
       if (SEG) ebuf = c < (uint32_t)Lmax ? ein[c & rmask] : make_uint2(as_u32(H0), as_u32(X0));
     }
-    // prefetching ring: the next block's codes go in before step T + 64's codes are read
-    if constexpr (RING && PF) {
+    // the ring's next block of codes goes in before step T + 64's codes are read
+    if constexpr (RING) {
       if (!even && (t & 63) == 63) ring_write(load_codes((uint32_t)t + 1u + lane));
     }
     const uint32_t inj = RING ? 0u : __builtin_amdgcn_readlane(buf, t & 63);
@@ -440,14 +426,9 @@ __device__ __forceinline__ uint2 wave_pair(const ScoreArgs& a, const uint8_t* pr
       upX = as_u16x2(as_u32(X0) == 0 ? dpp_shr1_zero(botX) : dpp_shr1(as_u32(X0), botX));
     }
     uint32_t rca = 0, rcb = 0;  // RING: the two letters of column t - lane
-    if constexpr (RING && PF) {
+    if constexpr (RING) {
       rca = nra;
       rcb = nrb;
-    } else if constexpr (RING) {
-      // (t & 62) is shared by the two steps of an iteration: one address add per two steps
-      const uint8_t* rp = cring + (64 - lane) + (t & 62);
-      rca = rp[even ? 0 : 1];
-      rcb = rp[even ? 128 : 129];
     } else if constexpr (F16 && PROF) {  // shift down one lane and add the lane's row offset
       uint32_t nl = inj;
       asm volatile("s_nop 1\n\tv_add_u32_dpp %0, %1, %2 wave_shr:1 row_mask:0xf bank_mask:0xf"
@@ -484,7 +465,7 @@ __device__ __forceinline__ uint2 wave_pair(const ScoreArgs& a, const uint8_t* pr
             lk.hi[4 * q + 3] = y.w;
           }
         }
-        if constexpr (RING && PF) {  // the next step's letters (block start: the new block)
+        if constexpr (RING) {  // the next step's letters (block start: the new block)
           const uint8_t* np = cring_l + ((t + 1) & 63);
           nra = np[0];
           nrb = np[128];
@@ -608,10 +589,7 @@ __device__ __forceinline__ void wave_split_block(const ScoreArgs& a, uint32_t* s
   uint32_t L = 0;
   if (lane < 2 * PPB) {
     const size_t t = 2 * first + lane;
-    if (t < n)
-      L = a.packed == SWK_PACK_RECORDS ? record_len(a.res + t * SWB_RECORD)
-          : a.ustride                     ? a.ulen
-                                          : a.lens[t];
+    if (t < n) L = target_len(a, t);
   }
 #pragma unroll
   for (int off = 2; off >= 1; off >>= 1) L = max(L, (uint32_t)__shfl_xor((int)L, off));
@@ -758,7 +736,8 @@ static hipError_t launch_wave(const ScoreArgs& a, uint32_t prof_bytes, hipStream
 // * the lane pipeline is 32 deep: a pair's fill and drain skew is 31 steps, not 63;
 // * each half's lane 0 takes the row -1 boundary (lane 32 would otherwise read lane 31's
 //   bottom row through wave_shr): one v_cndmask per moved value.
-// Each half keeps its own 128-byte code ring (targets A, B: [previous 32 | next 32] columns).
+// Each half keeps its own code ring of 128 16-bit entries (targets A, B: [previous 32 | next 32]
+// columns).
 // Returns the half's two bests (every lane of the half).
 // Balanced ranges (score_wave_half, ScoreArgs.wbal_blocks): a visit may run steps [t0, t1) of
 // the unit only (t0, t1 multiples of 32): it starts from the lane state a predecessor's head
@@ -767,10 +746,14 @@ static hipError_t launch_wave(const ScoreArgs& a, uint32_t prof_bytes, hipStream
 // running best, the diagonal above, the bottom row that moves down at the next step; the code
 // ring and the profile words of the first steps are rebuilt from the codes.
 constexpr int WBAL_WORDS = 2 * 16 + 4;  // state words per lane (K = 16)
+// The two-pairs kernel's LDS: wave 0's code ring at byte 0, the profile after it, the other
+// waves' rings after the profile.
+constexpr uint32_t HALF_LS = 2048;       // profile bytes per letter: 512 rows of {s, 1.0} words
+constexpr uint32_t HALF_RING = 512;      // a wave's code ring: 2 halves x 128 entries x 2 bytes
+constexpr uint32_t HALF_ABS_BASE = 512;  // LDS byte address of the profile: one ring on
 template <bool GOTOH>
-__device__ __forceinline__ uint2 wave_two_pairs(const ScoreArgs& a, const uint8_t* prof,
-                                                uint8_t* cring, int lane, size_t p0,
-                                                int t0 = 0, int t1 = 0x7FFFFFFF,
+__device__ __forceinline__ uint2 wave_two_pairs(const ScoreArgs& a, uint8_t* cring, int lane,
+                                                size_t p0, int t0 = 0, int t1 = 0x7FFFFFFF,
                                                 const uint32_t* sin = nullptr,
                                                 uint32_t* sout = nullptr) {
   constexpr int K = 16;
@@ -788,23 +771,23 @@ __device__ __forceinline__ uint2 wave_two_pairs(const ScoreArgs& a, const uint8_
   const uint8_t* pA = a.res;
   const uint8_t* pB = a.res;
   if (have) {
-    LA = rec ? record_len(a.res + tA * SWB_RECORD) : uni ? a.ulen : a.lens[tA];
-    LB = tB >= n ? 0u : rec ? record_len(a.res + tB * SWB_RECORD) : uni ? a.ulen : a.lens[tB];
+    LA = target_len(a, tA);
+    LB = tB >= n ? 0u : target_len(a, tB);
     pA = rec ? a.res + tA * SWB_RECORD + 6 : uni ? a.res + tA * a.ustride
                                                  : a.res + (LA ? a.offs[tA] : 0);
     const size_t tb = tB < n ? tB : tA;
     pB = rec ? a.res + tb * SWB_RECORD + 6 : uni ? a.res + tb * a.ustride
                                                  : a.res + (LB ? a.offs[tB] : 0);
   }
-  uint32_t Lh = max(LA, LB);
+  const PairTargets<const uint8_t*> tg{LA, LB, pA, pB};
+  uint32_t Lh = max(tg.LA, tg.LB);
   Lh = max(Lh, (uint32_t)__shfl_xor((int)Lh, 32));
   const int Lmax = (int)__builtin_amdgcn_readfirstlane(Lh);
-  const uint32_t pad = a.pad, PSb = a.PS;
+  const uint32_t pad = a.pad;
   const f16x2 NOE2 = as_f16x2(as_u16x2(a.f16_noe)), NE2 = as_f16x2(as_u16x2(a.f16_ne)),
               NO2 = as_f16x2(as_u16x2(a.f16_no));
   const uint32_t noe = as_u32(as_u16x2(NOE2)), ne = as_u32(as_u16x2(NE2)),
                  no = as_u32(as_u16x2(NO2));
-  (void)NO2;
   const u16x2 H0 = {0, 0};
   const u16x2 X0 = GOTOH ? (u16x2){0, 0} : as_u16x2(NOE2);  // F / T of row -1
   u16x2 Hl[K], Xl[K];
@@ -829,45 +812,30 @@ __device__ __forceinline__ uint2 wave_two_pairs(const ScoreArgs& a, const uint8_
     botH = __hip_atomic_load(sp + (2 * K + 2) * 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     botX = __hip_atomic_load(sp + (2 * K + 3) * 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-  const bool top = hl == 0;  // row -1 of this half's pair
-  // (SWK_HALF_DPPSEL) the boundary lanes 0 and 32, and row -1's H and F / T in VGPRs
+  // each half's lane 0 takes row -1 of its pair: the boundary lanes 0 and 32 (for VCC), and
+  // row -1's H and F / T in VGPRs
   const uint64_t topmask = 0x0000000100000001ull;
   uint32_t h0v = as_u32(H0), x0v = as_u32(X0);
   asm volatile("" : "+v"(h0v), "+v"(x0v));
-  (void)topmask;
   // the codes of column c of this half's targets (pad past the end) as {A, B << 8}
   const auto load_codes = [&](const uint32_t c) __attribute__((always_inline)) -> uint32_t {
-    uint32_t x = pad, y = pad;
-    if (nib) {
-      if (c < LA) x = (pA[c >> 1] >> (4 * (c & 1))) & 15u;
-      if (c < LB) y = (pB[c >> 1] >> (4 * (c & 1))) & 15u;
-    } else if (packed) {
-      if (c < LA) x = (pA[c >> 2] >> (2 * (c & 3))) & 3u;
-      if (c < LB) y = (pB[c >> 2] >> (2 * (c & 3))) & 3u;
-    } else {
-      if (c < LA) x = pA[c];
-      if (c < LB) y = pB[c];
-    }
-    return min(x, pad) | (min(y, pad) << 8);
+    const uint2 l = tg.codes(c, nib, packed, pad);
+    return l.x | (l.y << 8);
   };
-  // ring entries are profile offsets (letter x LS), 32-bit (or 16-bit loads that zero-extend):
-  // a byte entry read in one step and used in the next would be masked again in every basic
-  // block it crosses
-  typedef typename std::conditional<SWK_HALF_FMA != 0, uint16_t, uint32_t>::type RingT;
-  constexpr uint32_t LS = SWK_HALF_LS;
-  (void)PSb;
+  // ring entries are 16-bit (loads that zero-extend): a byte entry read in one step and used in
+  // the next would be masked again in every basic block it crosses
+  typedef uint16_t RingT;
   RingT* ring = reinterpret_cast<RingT*>(cring) + 128 * h;
   const RingT* ring_l = ring + 32 - hl;  // step T + j reads ring_l[j] (A), ring_l[64 + j] (B)
   uint32_t ringprev = pad | pad << 8;
-  // SWK_HALF_ABS: slot j of a half's ring (j in [0, 64): the window before and the current 32
-  // columns) holds the LDS byte address, from the block's LDS base, that lane hl needs at window
-  // step u when it reads slot j = 32 - hl + u, minus 16 u: the lane's rows of the column's letter
-  // sit at profile + letter x LS + 16 hl = (SWK_HALF_ABS_BASE + letter x LS + 16 (32 - j)) + 16 u,
+  // Slot j of a half's ring (j in [0, 64): the window before and the current 32 columns) holds
+  // the LDS byte address, from the block's LDS base, that lane hl needs at window step u when it
+  // reads slot j = 32 - hl + u, minus 16 u: the lane's rows of the column's letter sit at
+  // profile + letter x HALF_LS + 16 hl = (HALF_ABS_BASE + letter x HALF_LS + 16 (32 - j)) + 16 u,
   // so the step adds 16 u and the profile piece as load offsets (immediates once the window is
   // unrolled) and no address is computed.  Entries stay in [16, 65535] (24 letters x 2 KB).
   const auto ring_entry = [&](uint32_t letter, uint32_t j) __attribute__((always_inline)) {
-    return SWK_HALF_ABS ? (RingT)(SWK_HALF_ABS_BASE + letter * LS + 512u - 16u * j)
-                        : (RingT)(letter * LS);
+    return (RingT)(HALF_ABS_BASE + letter * HALF_LS + 512u - 16u * j);
   };
   const auto ring_write = [&](const uint32_t nc) __attribute__((always_inline)) {
     ring[hl] = ring_entry(ringprev & 0xFFu, hl);
@@ -884,20 +852,17 @@ __device__ __forceinline__ uint2 wave_two_pairs(const ScoreArgs& a, const uint8_
   uint32_t ncode = load_codes(c0 + 32u + hl);
   // score_wave_half's LDS copy of the profile keeps each letter's rows of every lane in 16-byte
   // pieces 512 bytes apart (piece q of lane l at 512 q + 16 l): a ds_read_b128 of 16 lanes then
-  // covers all 64 banks.  2-byte entries: 2 pieces (rows 0-7, 8-15); FMA words: 4 pieces.
-  typedef typename std::conditional<SWK_HALF_FMA != 0, ProfLookupF<K>, ProfLookupK16<K>>::type LK;
-  const uint8_t* plds = prof + hl * 16;
-  // (SWK_HALF_ABS: u = the step's place in the ring window, 16 u a load offset; a ring entry IS
-  // the LDS byte address: score_wave_half declares no static LDS, so its dynamic LDS -- the
-  // profile at SWK_HALF_ABS_BASE -- starts at LDS address 0.  An integer turned into an LDS
-  // pointer, because "dynamic LDS base + entry" keeps an add of the base symbol (0) per load
-  // address that LLVM does not fold.)
-  const auto load_prof = [&](auto& lk, uint32_t oa, uint32_t ob, uint32_t u = 0)
+  // covers all 64 banks.  The 16 {s, 1.0} words of a lane and letter are 4 pieces.
+  typedef ProfLookupF<K> LK;
+  // u = the step's place in the ring window, 16 u a load offset; a ring entry IS the LDS byte
+  // address: score_wave_half declares no static LDS, so its dynamic LDS -- the profile at
+  // HALF_ABS_BASE -- starts at LDS address 0.  An integer turned into an LDS pointer, because
+  // "dynamic LDS base + entry" keeps an add of the base symbol (0) per load address that LLVM
+  // does not fold.
+  const auto load_prof = [&](LK& lk, uint32_t oa, uint32_t ob, uint32_t u = 0)
                              __attribute__((always_inline)) {
-#if SWK_HALF_ABS
     typedef unsigned int v4u __attribute__((ext_vector_type(4)));
     typedef __attribute__((address_space(3))) const v4u lds_v4u;
-    (void)plds;
 #pragma unroll
     for (int q = 0; q < K / 4; ++q) {
       const v4u x = *reinterpret_cast<lds_v4u*>((uintptr_t)(oa + 16u * u + 512u * q));
@@ -905,54 +870,20 @@ __device__ __forceinline__ uint2 wave_two_pairs(const ScoreArgs& a, const uint8_
       lk.a[4 * q] = x.x; lk.a[4 * q + 1] = x.y; lk.a[4 * q + 2] = x.z; lk.a[4 * q + 3] = x.w;
       lk.b[4 * q] = y.x; lk.b[4 * q + 1] = y.y; lk.b[4 * q + 2] = y.z; lk.b[4 * q + 3] = y.w;
     }
-#else
-    (void)u;
-    const uint8_t* la = plds + oa;
-    const uint8_t* lb = plds + ob;
-    if constexpr (SWK_HALF_FMA) {
-#pragma unroll
-      for (int q = 0; q < K / 4; ++q) {
-        const uint4 x = *reinterpret_cast<const uint4*>(la + 512 * q);
-        const uint4 y = *reinterpret_cast<const uint4*>(lb + 512 * q);
-        lk.a[4 * q] = x.x; lk.a[4 * q + 1] = x.y; lk.a[4 * q + 2] = x.z; lk.a[4 * q + 3] = x.w;
-        lk.b[4 * q] = y.x; lk.b[4 * q + 1] = y.y; lk.b[4 * q + 2] = y.z; lk.b[4 * q + 3] = y.w;
-      }
-    } else {
-#pragma unroll
-      for (int q = 0; q < K / 8; ++q) {
-        const uint4 x = *reinterpret_cast<const uint4*>(la + 512 * q);
-        const uint4 y = *reinterpret_cast<const uint4*>(lb + 512 * q);
-        lk.lo[4 * q] = x.x; lk.lo[4 * q + 1] = x.y; lk.lo[4 * q + 2] = x.z; lk.lo[4 * q + 3] = x.w;
-        lk.hi[4 * q] = y.x; lk.hi[4 * q + 1] = y.y; lk.hi[4 * q + 2] = y.z; lk.hi[4 * q + 3] = y.w;
-      }
-    }
-#endif
   };
-  // AHEAD: a step's profile words are loaded during the step before (its ring entries two
-  // steps before), so no step waits on its own LDS reads: with 3-4 waves per SIMD the other
-  // waves hide less of that latency than the one-pair kernel's 6
-  constexpr bool AHEAD = SWK_HALF_AHEAD != 0;
+  // A step's profile words are loaded during the step before (its ring entries two steps
+  // before), so no step waits on its own LDS reads: with 3-4 waves per SIMD the other waves hide
+  // less of that latency than the one-pair kernel's 6
   LK lkn;
-  uint32_t nra, nrb;
-  if constexpr (AHEAD) {
-    load_prof(lkn, ring_l[0], ring_l[64]);
-    nra = ring_l[1];
-    nrb = ring_l[65];
-  } else {
-    nra = ring_l[0];
-    nrb = ring_l[64];
-  }
-  // AHEAD: step t reads the ring entries of step t + 2 at rp = ring_l + ((t + 2) & 31); a pair
-  // of steps from an even t never wraps, so one address per pair and immediate offsets.
-  // SWK_HALF_UNROLL: steps per loop iteration (2 or 4)
-  const RingT* rp = ring_l;
-#if SWK_HALF_ABS
+  load_prof(lkn, ring_l[0], ring_l[64]);
+  uint32_t nra = ring_l[1], nrb = ring_l[65];
   // one step at window place u (t & 31 == u): the ring refill at u = 30, the words of step t + 1
   // (place u + 1) and the ring entries of step t + 2 (place u + 2) read with constant offsets
   // when u is a constant (the unrolled window below), else (the last partial window) computed
-  const auto step_abs = [&](const int t, const int u) __attribute__((always_inline)) {
-    if (u == 30) {
+  const auto step = [&](const int t, const int u) __attribute__((always_inline)) {
+    if (u == 30) {  // the next 32 columns go in two steps before they are read
       ring_write(ncode);
+      // (t through an opaque copy: no per-step pointer increments for these loads)
       uint32_t tt = (uint32_t)t;
       asm volatile("" : "+s"(tt));
       ncode = load_codes(tt + 34u + hl);
@@ -962,7 +893,11 @@ __device__ __forceinline__ uint2 wave_two_pairs(const ScoreArgs& a, const uint8_
     nra = ring_l[(u + 2) & 31];
     nrb = ring_l[64 + ((u + 2) & 31)];
     __builtin_amdgcn_sched_barrier(0);
-    u16x2 upH, upX;
+    // the row above moves down and each half's lane 0 takes the row -1 boundary in one
+    // v_cndmask_b32_dpp per value.  Lanes 0 and 32 in VCC: v_cndmask_b32 D = VCC ? src1 : src0,
+    // src0 read through wave_shr:1 (bound_ctrl: lane 0 reads 0 and is written); s_nop 1: the two
+    // wait states a DPP read needs after the VALU write of its source (inside asm LLVM inserts
+    // none)
     uint32_t uh, ux;
     asm volatile(
         "s_nop 1\n\t"
@@ -972,92 +907,24 @@ __device__ __forceinline__ uint2 wave_two_pairs(const ScoreArgs& a, const uint8_
         : [uh] "=&v"(uh), [ux] "=&v"(ux)
         : [bh] "v"(botH), [bx] "v"(botX), [h0] "v"(h0v), [x0] "v"(x0v), [m] "s"(topmask)
         : "vcc");
-    upH = as_u16x2(uh);
-    upX = as_u16x2(ux);
+    const u16x2 upH = as_u16x2(uh);
+    u16x2 upX = as_u16x2(ux);
     u16x2 diag = prevUpH;
     prevUpH = upH;
     __builtin_amdgcn_sched_barrier(0);
-    column_f16_lane_asm<K, GOTOH>(lk, diag, upX, Hl, Xl, best, noe, ne, no);
-    asm volatile("" : "+v"(best));
-    botH = as_u32(Hl[K - 1]);
-    botX = as_u32(upX);
-  };
-#endif
-  const auto step = [&](const int t, const bool even) __attribute__((always_inline)) {
-    // the next 32 columns go in before they are read (AHEAD: two steps before)
-    if ((AHEAD ? even : !even) && (t & 31) == (AHEAD ? 30 : 31)) {
-      ring_write(ncode);
-      // (t through an opaque copy: no per-step pointer increments for these loads)
-      uint32_t tt = (uint32_t)t;
-      asm volatile("" : "+s"(tt));
-      ncode = load_codes(tt + (AHEAD ? 34u : 33u) + hl);
-    }
-    LK lk;
-    if constexpr (AHEAD) {
-      lk = lkn;
-      load_prof(lkn, nra, nrb);
-      const RingT* np = rp + (even ? 0 : 1);  // (t is even in an even step: an immediate offset)
-      nra = np[0];
-      nrb = np[64];
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    u16x2 upH, upX;
-    if constexpr (SWK_HALF_DPPSEL != 0) {
-      // lanes 0 and 32 in VCC: v_cndmask_b32 D = VCC ? src1 : src0, src0 read through
-      // wave_shr:1 (bound_ctrl: lane 0 reads 0 and is written); s_nop 1: the two wait states a
-      // DPP read needs after the VALU write of its source (inside asm LLVM inserts none)
-      uint32_t uh, ux;
-      asm volatile(
-          "s_nop 1\n\t"
-          "s_mov_b64 vcc, %[m]\n\t"
-          "v_cndmask_b32_dpp %[uh], %[bh], %[h0], vcc wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-          "v_cndmask_b32_dpp %[ux], %[bx], %[x0], vcc wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1"
-          : [uh] "=&v"(uh), [ux] "=&v"(ux)
-          : [bh] "v"(botH), [bx] "v"(botX), [h0] "v"(h0v), [x0] "v"(x0v), [m] "s"(topmask)
-          : "vcc");
-      upH = as_u16x2(uh);
-      upX = as_u16x2(ux);
-    } else {
-      upH = as_u16x2(dpp_shr1_zero(botH));
-      upX = as_u16x2(GOTOH ? dpp_shr1_zero(botX) : dpp_shr1(as_u32(X0), botX));
-      upH = top ? H0 : upH;
-      upX = top ? X0 : upX;
-    }
-    u16x2 diag = prevUpH;
-    prevUpH = upH;
-    __builtin_amdgcn_sched_barrier(0);
-    if constexpr (!AHEAD) {
-      load_prof(lk, nra, nrb);
-      const RingT* np = ring_l + ((t + 1) & 31);  // the next step's profile offsets
-      nra = np[0];
-      nrb = np[64];
-    }
     column_f16_lane_asm<K, GOTOH>(lk, diag, upX, Hl, Xl, best, noe, ne, no);
     asm volatile("" : "+v"(best));
     botH = as_u32(Hl[K - 1]);
     botX = as_u32(upX);
   };
   const int nsteps = min(Lmax + 31, t1);
-#if SWK_HALF_ABS
-  (void)step;
-  (void)rp;
   // whole 32-step windows unrolled (t0 is a multiple of 32), then the last partial window
   int t = t0;
   for (; t + 32 <= nsteps; t += 32) {
 #pragma unroll
-    for (int u = 0; u < 32; ++u) step_abs(t + u, u);
+    for (int u = 0; u < 32; ++u) step(t + u, u);
   }
-  for (; t < nsteps; ++t) step_abs(t, t & 31);
-#else
-  for (int t = t0; t < nsteps; t += SWK_HALF_UNROLL) {
-#pragma unroll
-    for (int u = 0; u < SWK_HALF_UNROLL; u += 2) {
-      rp = ring_l + ((t + u + 2) & 31);
-      step(t + u, true);
-      step(t + u + 1, false);
-    }
-  }
-#endif
+  for (; t < nsteps; ++t) step(t, t & 31);
   if (sout) {  // a head visit: the lane state for the successor's tail visit (sc1 stores)
     uint32_t* sp = sout + lane;
 #pragma unroll
@@ -1296,52 +1163,41 @@ __global__ void __launch_bounds__(64 * W, W == 8 ? 4 : 1) score_wave_half(const 
       const unsigned u = (blockIdx.x - a.split_blocks - mb) * 4 + wave;
       // the tail waves are the youngest on their SIMDs: without the top priority the SIMD's
       // oldest-first issue starves their segment chain behind the main waves
-      if (SWK_TAIL_TOP) __builtin_amdgcn_s_setprio(3);
+      __builtin_amdgcn_s_setprio(3);
       if (u < a.tail_pairs * a.split_P)
         wave_tail_seg<GOTOH>(a, prof + (size_t)wave * a.split_words * 4, lane, u);
       return;
     }
   }
-  if constexpr (SWK_HALF_FMA) {
-    // the K = 8 profile (2-byte entries, PS = 1024 bytes per letter) as words {s, 1.0}, 2048
-    // bytes per letter: row r = 16 l + 4 q + j (lane l of a half, piece q, word j) at word
-    // 128 q + 4 l + j, so lane l reads its 16 rows as 4 x 16 bytes, 512 apart
-    // (16-byte loads of 8 entries, rows 8 m .. 8 m + 7 of a letter = pieces q, q + 1 of lane
-    // l: two 16-byte LDS stores; the loads of a thread's iterations are independent)
-    const uint32_t groups = (a.pad + 1) * 64;
-    const uint4* src = reinterpret_cast<const uint4*>(a.qtab);
-    uint4* dst = reinterpret_cast<uint4*>(prof + (SWK_HALF_ABS ? SWK_HALF_ABS_BASE : 0u));
-    const auto widen = [](uint32_t x) {  // two entries -> two {s, 1.0} words
-      return make_uint2((x & 0xFFFFu) | 0x3C000000u, (x >> 16) | 0x3C000000u);
-    };
+  // the K = 8 profile (2-byte entries, PS = 1024 bytes per letter) as words {s, 1.0}, 2048
+  // bytes per letter: row r = 16 l + 4 q + j (lane l of a half, piece q, word j) at word
+  // 128 q + 4 l + j, so lane l reads its 16 rows as 4 x 16 bytes, 512 apart
+  // (16-byte loads of 8 entries, rows 8 m .. 8 m + 7 of a letter = pieces q, q + 1 of lane
+  // l: two 16-byte LDS stores; the loads of a thread's iterations are independent)
+  const uint32_t groups = (a.pad + 1) * 64;
+  const uint4* src = reinterpret_cast<const uint4*>(a.qtab);
+  uint4* dst = reinterpret_cast<uint4*>(prof + HALF_ABS_BASE);
+  const auto widen = [](uint32_t x) {  // two entries -> two {s, 1.0} words
+    return make_uint2((x & 0xFFFFu) | 0x3C000000u, (x >> 16) | 0x3C000000u);
+  };
 #pragma unroll 4
-    for (uint32_t i = threadIdx.x; i < groups; i += blockDim.x) {
-      const uint4 v = src[i];
-      const uint32_t r = (i & 63u) * 8;  // first row of the group
-      const uint32_t w = (i & ~63u) * 8 | ((r >> 2) & 3u) << 7 | (r >> 4) << 2;  // word index
-      const uint2 a0 = widen(v.x), a1 = widen(v.y), a2 = widen(v.z), a3 = widen(v.w);
-      dst[w / 4] = make_uint4(a0.x, a0.y, a1.x, a1.y);            // rows r .. r + 3
-      dst[w / 4 + 32] = make_uint4(a2.x, a2.y, a3.x, a3.y);       // rows r + 4 .. r + 7
-    }
-    __syncthreads();
-#if SWK_STAMPS
-    st_copy = __builtin_amdgcn_s_memtime();
-#endif
-  } else {  // the K = 8 profile (64 16-byte row groups per letter, PS = 1024) with group 2l + q
-            // at 32 q + l: lane l of a half reads its rows 16 l .. 16 l + 15 as 16 + 16 bytes,
-            // 512 apart
-    const uint32_t words = (a.pad + 1) * a.PS / 16;
-    const uint4* src = reinterpret_cast<const uint4*>(a.qtab);
-    for (uint32_t i = threadIdx.x; i < words; i += blockDim.x)
-      reinterpret_cast<uint4*>(prof)[(i & ~63u) | (i & 1u) << 5 | (i & 63u) >> 1] = src[i];
-    __syncthreads();
+  for (uint32_t i = threadIdx.x; i < groups; i += blockDim.x) {
+    const uint4 v = src[i];
+    const uint32_t r = (i & 63u) * 8;  // first row of the group
+    const uint32_t w = (i & ~63u) * 8 | ((r >> 2) & 3u) << 7 | (r >> 4) << 2;  // word index
+    const uint2 a0 = widen(v.x), a1 = widen(v.y), a2 = widen(v.z), a3 = widen(v.w);
+    dst[w / 4] = make_uint4(a0.x, a0.y, a1.x, a1.y);            // rows r .. r + 3
+    dst[w / 4 + 32] = make_uint4(a2.x, a2.y, a3.x, a3.y);       // rows r + 4 .. r + 7
   }
+  __syncthreads();
+#if SWK_STAMPS
+  st_copy = __builtin_amdgcn_s_memtime();
+#endif
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  // (SWK_HALF_ABS: wave 0's ring at byte 0, the profile from SWK_HALF_ABS_BASE = one ring on)
-  uint8_t* mprof = prof + (SWK_HALF_ABS ? SWK_HALF_ABS_BASE : 0u);
-  uint8_t* cring = SWK_HALF_ABS && wave == 0
-                       ? prof
-                       : mprof + (a.pad + 1) * SWK_HALF_LS + SWK_HALF_RING * (wave - (SWK_HALF_ABS ? 1 : 0));
+  // wave 0's ring at byte 0, the profile from HALF_ABS_BASE = one ring on, the other waves'
+  // rings after the profile
+  uint8_t* cring =
+      wave == 0 ? prof : prof + HALF_ABS_BASE + (a.pad + 1) * HALF_LS + HALF_RING * (wave - 1);
   // Balanced ranges (ScoreArgs.wbal_blocks): wave g of the G resident waves scores
   // blocks [A_g, A_g+1) of the unit-major sequence of 32-step blocks, A_g = g U B / G (U units
   // of two pairs, B blocks each), so every wave slot gets the same number of steps whatever
@@ -1395,7 +1251,7 @@ __global__ void __launch_bounds__(64 * W, W == 8 ? 4 : 1) score_wave_half(const 
 #endif
     }
     const uint2 b = wave_two_pairs<GOTOH>(
-        a, mprof, cring, lane, 2 * (size_t)unit, tail ? 32 * b0 : 0, head ? 32 * b1 : 0x7FFFFFFF,
+        a, cring, lane, 2 * (size_t)unit, tail ? 32 * b0 : 0, head ? 32 * b1 : 0x7FFFFFFF,
         tail ? a.bal_state + (size_t)g * sw : nullptr,
         head ? a.bal_state + (size_t)(g + 1) * sw : nullptr);
     if (head) {  // the lane state is out: wave g + 1 may take the unit on
@@ -1442,10 +1298,10 @@ __device__ __forceinline__ void wave_half_finish(const ScoreArgs& a, uint2 b, in
 }
 
 
-// the main blocks' LDS: the profile (prof_bytes at PS = 1024: 2 bytes per letter and row;
-// SWK_HALF_FMA: 4) + each wave's code rings
+// the main blocks' LDS: the profile (prof_bytes counts 2 bytes per letter and row at PS = 1024;
+// the kernel's {s, 1.0} words take 4) + each wave's code ring
 static size_t wave_half_lds(uint32_t prof_bytes, int W) {
-  return (size_t)prof_bytes / 1024 * SWK_HALF_LS + SWK_HALF_RING * (size_t)W;
+  return (size_t)prof_bytes / 1024 * HALF_LS + HALF_RING * (size_t)W;
 }
 
 template <bool GOTOH, int W>
@@ -1466,12 +1322,12 @@ static hipError_t launch_wave_half(const ScoreArgs& a, uint32_t prof_bytes, hipS
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return e;
-    // SWK_HALF_ABS: the ring entries are LDS addresses counted from 0, which holds only while
+    // the ring entries are LDS addresses counted from 0, which holds only while
     // the kernel has no static LDS (its dynamic LDS then starts at 0)
     hipFuncAttributes fa;
     e = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(fn));
     if (e != hipSuccess) return e;
-    if (SWK_HALF_ABS && fa.sharedSizeBytes != 0) return hipErrorInvalidConfiguration;
+    if (fa.sharedSizeBytes != 0) return hipErrorInvalidConfiguration;
     attr_set = true;
   }
   if (lds > 160 * 1024) return hipErrorInvalidConfiguration;
