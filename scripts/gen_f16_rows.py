@@ -42,7 +42,8 @@ equals v_pk_add_f16's).  So a profile row costs 7.5 VALU (Gotoh) / 5.5 (merged) 
 the DNA letter-pair table, without a table per letter pair.
 
 Skewed merged pair rows (SWK_F16SKEW_F/M/L, skew_pair_block below): cells in anti-diagonal
-frames, 5 VALU per row with the letter-pair table holding s + 2e.
+frames that restart every 8 rows, 4.75 VALU per row with the letter-pair table holding s + 2e
+(s + 2e - 8e in a block's first row).
 
 No two dependent packed (VOP3P) ops are adjacent (gfx950 needs a wait state between them;
 v_perm_b32 -> VOP3P needs none), so a block needs no s_nop inside; LLVM adds one wait state
@@ -152,43 +153,108 @@ def pair_gotoh_block(first, last, nrows=8):
     return out + gotoh_block("pair", last, nrows)
 
 
-def skew_pair_block(first, last, nrows=8):
-    """Pair-profile block in anti-diagonal frames (DNA, merged gaps, DESIGN 3.1 "skewed rows"):
-    cell (i, j) is held with the offset c_k = e (k - 1), k = i + j, so the gap extension is
-    paid by the frame and a row is 4 VALU, plus one add and one max3 per two rows for the best:
+SKEW_ACC = 4  # accumulators of the running best (csrc: SWK_SKEW_ACC)
+
+
+def _regs(ln):
+    """(destination, sources) of one generated line."""
+    op, rest = ln.split(None, 1)
+    ops = [x.strip() for x in rest.split(",")]
+    return ops[0], ops[1:]
+
+
+def check_no_adjacent_dependence(lines):
+    """No instruction reads the register the one before it wrote."""
+    for a, b in zip(lines, lines[1:]):
+        if a.startswith("s_nop") or b.startswith("s_nop"):
+            continue
+        assert _regs(a)[0] not in _regs(b)[1], (a, b)
+    return lines
+
+
+def skew_pair_block(kind, nrows=8):
+    """Pair-profile block in block frames (DNA, merged gaps, DESIGN 3.1 "skewed rows"): cell
+    (i, j) is held with the offset c_f = e (f - 1), f = (i mod 8) + j, so the gap extension is
+    paid by the frame and a row is 4 VALU:
 
         A'  = Hl(old) + p            next row's A = H^(i-1,j-1) + (s + 2e)   (no clamp)
-        T~  = max3(AO, Tup, Tl) -> Tl   (= G + c_k: what the right and lower cells read)
+        T~  = max3(AO, Tup, Tl) -> Tl   (= G + c_f: what the right and lower cells read)
         AO' = A' + (-o)              next row's A - o
-        H^  = max3(T~, A, c_k)  -> Hl   c_k: the frame's floor (H = 0), an SGPR per row
-        best = best + 2e             even rows: the running best moved two frames on
-        best = max3(best, H^(i-1,j) new, H^(i,j-1) old)  odd rows, before row i's H^ is written
+        H^  = max3(T~, A, c_f)  -> Hl   c_f: the frame's floor (H = 0), an SGPR per row
 
-    The first block forms row 0's A and A - o from dg + pw and moves the best from the last
-    pair of the previous column to the first of this one (e2f = (3 - rows per wave) e).  AO
-    runs one row ahead through the blocks like Da; no two dependent packed ops are adjacent."""
-    out = []
+    A block's first row sits 7 frames before the row above it: its table word holds s + 2e - 8e
+    (no instruction) and its Tup is shifted once, Tup + (-8e).  kind "F" (a column's first
+    block) forms row 0's A and A - o from dg + pw and shifts the ring entry in place; every
+    block but the last ends by shifting its last T~ into Db for the block below, which reads it
+    before it writes Db ("M", "L": Da, AO and Db come in).  AO runs one row ahead.
+
+    The best: rows u, u + 8, u + 16, u + 24 of a column share frame u + j, so two max3 fold the
+    four (g: rows 0-7, k: 8-15, m: 16-23 of the column, h: the last block's own) into
+    accumulator b[u / 2], which makes one + e move per column, between its classes 2a and
+    2a + 1, and none to the next column (class 2a of column j + 1 has the frame of class 2a + 1
+    of column j).  The folds go into the last block, between the rows' dependent pairs; the
+    last accumulator's move and class 7 (row 7 of the last block ends the column) into the
+    first block of the next column, before it overwrites row 7: x, y, z = rows 15, 23, 31.
+    16 max3 and 4 adds per column: 4.75 VALU per row with the 4 shifts."""
+    assert nrows == 8 and SKEW_ACC == 4
+    rows = []  # per row: [nd, tt, ao, hh]
     for i in range(nrows):
         dcur, dnext = ("%[Da]", "%[Db]") if i % 2 == 0 else ("%[Db]", "%[Da]")
-        up = "%[up]" if i == 0 else f"%[t{i - 1}]"
-        final = last and i == nrows - 1
-        nd = f"v_pk_add_f16 {dnext}, %[h{i}], %[p{i}]"
-        ao = f"v_pk_add_f16 %[AO], {dnext}, %[no]"
-        tt = f"v_pk_maximum3_f16 %[t{i}], %[AO], {up}, %[t{i}]"
-        hh = f"v_pk_maximum3_f16 %[h{i}], %[t{i}], {dcur}, %[c{i}]"
-        if i % 2 == 0:
-            step = "%[e2f]" if first and i == 0 else "%[e2]"
-            bt = f"v_pk_add_f16 %[best], %[best], {step}"
-            if first and i == 0:
-                out += ["v_pk_add_f16 %[Da], %[dg], %[pw]", nd,
-                        "v_pk_add_f16 %[AO], %[Da], %[no]", bt, tt, ao, hh]
-            else:
-                out += [nd, tt, ao, bt, hh]
-        else:
-            bb = f"v_pk_maximum3_f16 %[best], %[best], %[h{i - 1}], %[h{i}]"
-            out += [tt, bb, hh] if final else [nd, bb, tt, ao, hh]
-    assert nrows % 2 == 0
-    return out
+        up = ("%[up]" if kind == "F" else "%[Db]") if i == 0 else f"%[t{i - 1}]"
+        rows.append([f"v_pk_add_f16 {dnext}, %[h{i}], %[p{i}]",
+                     f"v_pk_maximum3_f16 %[t{i}], %[AO], {up}, %[t{i}]",
+                     f"v_pk_add_f16 %[AO], {dnext}, %[no]",
+                     f"v_pk_maximum3_f16 %[h{i}], %[t{i}], {dcur}, %[c{i}]"])
+    shift = f"v_pk_add_f16 %[Db], %[t{nrows - 1}], %[ne8]"
+    if kind == "F":
+        nd, tt, ao, hh = rows[0]
+        out = ["v_pk_add_f16 %[Da], %[dg], %[pw]", "v_pk_add_f16 %[up], %[up], %[ne8]", nd,
+               "v_pk_add_f16 %[AO], %[Da], %[no]", "v_pk_add_f16 %[b3], %[b3], %[e1]", tt, ao,
+               "v_pk_maximum3_f16 %[b3], %[b3], %[h7], %[x]", hh]
+        nd, tt, ao, hh = rows[1]
+        out += [nd, tt, "v_pk_maximum3_f16 %[b3], %[b3], %[y], %[z]", ao, hh]
+        for r in rows[2:]:
+            out += r
+        return check_no_adjacent_dependence(out + [shift])
+    nd, tt, ao, hh = rows[0]
+    base = [tt, nd, hh, ao]  # (Db: the shifted Tup, read before the next row's A goes there)
+    if kind == "M":
+        for r in rows[1:]:
+            base += r
+        return check_no_adjacent_dependence(base + [shift])
+    assert kind == "L"
+    for r in rows[1:-1]:
+        base += r
+    base += [rows[-1][1], rows[-1][3]]  # the column's last row has no successor
+    # the folds: per accumulator a chain; (line, the row of this block it waits for or None)
+    chains = []
+    for a in range(SKEW_ACC):
+        u, v, b = 2 * a, 2 * a + 1, f"%[b{a}]"
+        ch = [(f"v_pk_maximum3_f16 {b}, {b}, %[g{u}], %[k{u}]", None),
+              (f"v_pk_maximum3_f16 {b}, {b}, %[m{u}], %[h{u}]", u)]
+        if a < SKEW_ACC - 1:
+            ch += [(f"v_pk_add_f16 {b}, {b}, %[e1]", None),
+                   (f"v_pk_maximum3_f16 {b}, {b}, %[g{v}], %[k{v}]", None),
+                   (f"v_pk_maximum3_f16 {b}, {b}, %[m{v}], %[h{v}]", v)]
+        chains.append(ch)
+    out, done = [], set()  # done: rows of this block whose H^ is written
+    turn = 0
+    for ln in base:
+        out.append(ln)
+        d = _regs(ln)[0]
+        if ln.startswith("v_pk_maximum3") and d.startswith("%[h"):
+            done.add(int(d[3:-1]))
+        for k in range(SKEW_ACC):  # one fold after each row instruction, accumulators in turn
+            ch = chains[(turn + k) % SKEW_ACC]
+            if not ch:
+                continue
+            f, wait = ch[0]
+            if (wait is None or wait in done) and _regs(out[-1])[0] not in _regs(f)[1]:
+                out.append(ch.pop(0)[0])
+                turn = (turn + k + 1) % SKEW_ACC
+                break
+    assert not any(chains), chains
+    return check_no_adjacent_dependence(out)
 
 
 def fmt(lines):
@@ -222,9 +288,8 @@ def main():
     parts.append("#define SWK_F16PAIRG_F \\\n" + fmt(pair_gotoh_block(True, False)))
     parts.append("#define SWK_F16PAIRG_M \\\n" + fmt(pair_gotoh_block(False, False)))
     parts.append("#define SWK_F16PAIRG_L \\\n" + fmt(pair_gotoh_block(False, True)))
-    parts.append("#define SWK_F16SKEW_F \\\n" + fmt(skew_pair_block(True, False)))
-    parts.append("#define SWK_F16SKEW_M \\\n" + fmt(skew_pair_block(False, False)))
-    parts.append("#define SWK_F16SKEW_L \\\n" + fmt(skew_pair_block(False, True)))
+    for kind in "FML":
+        parts.append(f"#define SWK_F16SKEW_{kind} \\\n" + fmt(skew_pair_block(kind)))
     # mode F (profile words {s, 1.0}: one packed FMA per row, no lookup), 8-row blocks
     for last in (0, 1):
         parts.append(f"#define SWK_F16M_F_Z0_L{last} \\\n" + fmt(merged_block("F", 0, last)))

@@ -406,9 +406,10 @@ struct sw_bank {
   DevBuf<uint32_t> qpair;
   uint32_t pair_bytes = 0, pS1 = 0, pS2 = 0;
   // the skewed rows of the merged pair kernel: a second pair table holding s + 2e
-  // (same layout; rows past the query -skew_pad + 2e) and the frames' floors skew_ctab[k + 2] =
-  // c_k = e (k - 1), skew_entries words.  skew_neg: the most negative value a skewed column
-  // forms; skew_entries = 0 when the query has no merged pair table
+  // (same layout; the first row of every 8-row block s + 2e - 8e; rows past the query the pad
+  // score -skew_pad in place of s) and the frames' floors skew_ctab[k + 2] = c_k = e (k - 1),
+  // skew_entries words.  skew_neg: the most negative value of a skewed column that has to be
+  // exact; skew_entries = 0 when the query has no merged pair table
   DevBuf<uint32_t> qpair_skew, skew_ctab;
   uint32_t skew_entries = 0;
   int32_t skew_neg = 0;

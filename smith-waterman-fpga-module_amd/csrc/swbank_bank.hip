@@ -525,18 +525,20 @@ static void pair_strides(uint32_t NR, uint32_t& pS1, uint32_t& pS2) {
 // slot (a, b) holds word k = {s(q_{r0+k+1}, a), s(q_{r0+k+1}, b)} (f16 halves; rows past the
 // query -2048) and the row-r0 word 4 bytes before it.
 // add / pad: the skewed rows' table holds s + add (add = 2e) and pad + add in rows past the query
-// (the unskewed kernel's: s, -2048).
+// (the unskewed kernel's: s, -2048); add0: what the first row of every 8-row block holds on top
+// (the skewed rows' -8e: the row above it sits 7 frames on), pad rows too.
 static std::vector<uint32_t> pair_table(const uint8_t* q, int qlen, int r0, uint32_t NR,
                                         const int8_t* m, int A, uint32_t pS1, uint32_t pS2,
-                                        int add = 0, int pad = -2048) {
+                                        int add = 0, int pad = -2048, int add0 = 0) {
   const uint32_t bytes = 16 + 4 * pS1 + 4 * pS2 + 4 * NR;
   const uint32_t padw = (uint32_t)f16_score_bits(pad + add) * 0x10001u;
   std::vector<uint32_t> t(bytes / 4, padw);
   auto word = [&](int r, int x, int y) -> uint32_t {  // row r of the segment, letters x, y
-    if (r0 + r >= qlen) return padw;
+    const int ad = add + (r % 8 == 0 ? add0 : 0);
+    if (r0 + r >= qlen) return (uint32_t)f16_score_bits(pad + ad) * 0x10001u;
     const int c = q[r0 + r];
-    return (uint32_t)f16_score_bits(m[c * A + x] + add) |
-           (uint32_t)f16_score_bits(m[c * A + y] + add) << 16;
+    return (uint32_t)f16_score_bits(m[c * A + x] + ad) |
+           (uint32_t)f16_score_bits(m[c * A + y] + ad) << 16;
   };
   for (int x = 0; x < A; ++x)
     for (int y = 0; y < A; ++y) {
@@ -722,21 +724,25 @@ sw_status prepare(sw_bank* b) {
       tpair.insert(tpair.end(), t.begin(), t.end());
     }
   }
-  // The skewed rows of the merged pair kernel: the same table with s + 2e, rows
-  // past the query with a score no H can lift above 0 (H <= max(s) x rows), and the floors
-  // c_k = e (k - 1) of the anti-diagonal frames, word k + 2 (k = -2 ..: the diagonal above a
-  // tile's first cell).  launch() takes them when a batch's values fit f16 with the offsets.
+  // The skewed rows of the merged pair kernel: the same table with s + 2e (the
+  // first row of every 8-row block s + 2e - 8e), rows past the query with a score no H can lift
+  // above 0 (H <= max(s) x rows; the same score in every row, so that skew_neg, and with it
+  // launch()'s choice, is what it was before the frames restarted every 8 rows), and the floors
+  // c_k = e (k - 1) of the frames k = (row mod 8) + column, word k + 2.  launch() takes them when
+  // a batch's values fit f16 with the offsets.
   std::vector<uint32_t> tskew, tfloor;
   int skew_neg = 0;
   if (!tpair.empty() && !gotoh && 2 * e <= 2048) {
     const int spad = -std::min(2048 - 2 * e, S * std::max(qlen, 1));
     tskew = pair_table(b->query.data(), qlen, 0, (uint32_t)segs[0].W * R, m, A, pS1, pS2, 2 * e,
-                       spad);
-    tfloor.resize(2048 + 192);
+                       spad, -8 * e);
+    tfloor.resize(2048 + 32);
     for (size_t k = 0; k < tfloor.size(); ++k)
       tfloor[k] = (uint32_t)f16_score_bits(std::min(2048, e * ((int)k - 3))) * 0x10001u;
-    // the most negative value: A - o in the first frame, A = c_{-2} + min(s, pad) + 2e
-    skew_neg = -3 * e + std::min(smin, spad) + 2 * e - o;
+    // the most negative value that has to be exact: A - o of a block's first row in frame 0,
+    // A = c_6 + min(s, pad) + 2e - 8e.  (The T~ of the row above, shifted into that frame, can
+    // lie e lower; it is far below every floor and only ever enters a max)
+    skew_neg = 5 * e + std::min(smin, spad) + 2 * e - 8 * e - o;
   }
   // wave-kernel layout of the same query: rows padded to 64K; queries past 1024 rows run as
   // 1024-row segments (K = 16), one table per segment, concatenated

@@ -70,6 +70,12 @@ static inline int swk_wbal_admissible(unsigned long long U, unsigned long long B
   return (W == 4 || W == 8) && grid != 0 && U * B >= 4ull * W * grid;
 }
 
+/* Accumulators of the running best in the skewed rows of the tile kernel (the
+ * generator's SKEW_ACC), and the words per lane of a wave's balanced hand-off state: H^ and T~
+ * of R rows, the diagonal above, the accumulators (the unskewed rows have one best). */
+#define SWK_SKEW_ACC 4
+#define SWK_BAL_WORDS(R, ACC) (2 * (R) + 1 + (ACC))
+
 /* Kinds of a launch's fault marks (cross-workgroup hand-off waits that ran out).  Each kind has
  * its own word in the call's group of SWK_FAULT_WORDS words (word ctz(bit) holds bit), so a call
  * whose launches run out in two kinds keeps both (a plain store per kind, no read-modify-write

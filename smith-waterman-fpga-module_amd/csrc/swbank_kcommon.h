@@ -786,12 +786,14 @@ struct ScoreArgs {
   // honoured) while its codes, offsets and lengths are read at k (a copy of the batch in its
   // visiting order, SWBANK_RAGGED_GATHER)
   const uint32_t* sidx;
-  // (SKEW variants) cells in anti-diagonal frames: ctab[k + 2] = f16_pair(c_k), the
-  // floor c_k = e (k - 1) of frame k = query row + tile column, for k = -2 .. rows + columns + 40
-  // (a wave reads a 40-word slice per chunk with scalar loads); qtab then holds s + 2e.
-  // f16_e2 = f16_pair(2e), f16_e2f = f16_pair((3 - R) e): the running best's frame steps
+  // (SKEW variants) cells in anti-diagonal frames that restart every 8 rows:
+  // ctab[k + 2] = f16_pair(c_k), the floor c_k = e (k - 1) of frame k = (query row mod 8) + tile
+  // column, for k = -2 .. columns + 16 (a wave reads a 15-word slice per chunk with scalar
+  // loads); qtab then holds s + 2e, and s + 2e - 8e in a block's first row.
+  // f16_e1 = f16_pair(e): an accumulator of the running best moves one frame on;
+  // f16_ne8 = f16_pair(-8e): T~ of the row above a block's first row, brought into its frame
   const uint32_t* ctab;
-  uint32_t f16_e2, f16_e2f;
+  uint32_t f16_e1, f16_ne8;
 };
 static_assert(sizeof(ScoreArgs) == 392, "ScoreArgs layout (kernel argument block) changed");
 

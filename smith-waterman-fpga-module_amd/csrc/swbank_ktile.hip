@@ -4,6 +4,30 @@
 
 namespace swk {
 
+// tile_chunks for the SKEW kernels: the same counts, with the shuffle addresses formed from an
+// opaque copy of the lane at each call.  __shfl_xor's addresses depend on the lane alone, LLVM
+// hoists them out of the phase loop (3 VGPRs for the steps DPP cannot do), and the skewed column
+// has none to spare.
+template <int C>
+__device__ __forceinline__ void tile_chunks_local(const Lane2& t, size_t tlo, size_t thi, size_t n,
+                                                  int lane, int& nch, int& nfull, int& ncl) {
+  uint32_t Lmax = max(t.llo, t.lhi);
+  uint32_t Lmin = min(tlo < n ? t.llo : ~0u, thi < n ? t.lhi : ~0u);
+  uint32_t ol = (uint32_t)lane;
+  asm volatile("" : "+v"(ol));
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const int ad = (int)((ol ^ (uint32_t)off) << 2);
+    Lmax = max(Lmax, (uint32_t)__builtin_amdgcn_ds_bpermute(ad, (int)Lmax));
+    Lmin = min(Lmin, (uint32_t)__builtin_amdgcn_ds_bpermute(ad, (int)Lmin));
+  }
+  const int lx = (int)__builtin_amdgcn_readfirstlane(Lmax);
+  nch = max(1, (lx + C - 1) / C);
+  ncl = lx == 0 ? C : lx - C * (nch - 1);
+  const uint32_t lm = __builtin_amdgcn_readfirstlane(Lmin);
+  nfull = lm == ~0u ? 0 : (int)(lm / C);  // no valid lane (a tile past the end): no full loads
+}
+
 // C: columns per chunk (one barrier per chunk); 4 for the 16-wave query-set pair kernel, whose
 // hand-off ring would not fit LDS beside a 512-row pair table at 8.
 // TRIM: a tile's last chunk stops after its last column holding a code of some lane (ragged
@@ -197,8 +221,12 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
                             a.ustride);
   }
   int nch, nfull, ncl;
-  tile_chunks<C>(cur, (size_t)tile * SWB_TILE + lane, (size_t)tile * SWB_TILE + lane + 64, n, nch,
-              nfull, ncl);
+  if constexpr (SKEW)
+    tile_chunks_local<C>(cur, (size_t)tile * SWB_TILE + lane, (size_t)tile * SWB_TILE + lane + 64,
+                         n, lane, nch, nfull, ncl);
+  else
+    tile_chunks<C>(cur, (size_t)tile * SWB_TILE + lane, (size_t)tile * SWB_TILE + lane + 64, n,
+                   nch, nfull, ncl);
   (void)ncl;
   if constexpr (BAL) {  // BAL: nch = the visit's end chunk (a head's last chunk is whole)
     if (vend >= 0 && vend < nch) ncl = C;
@@ -211,32 +239,47 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
   // f16 encodings of -(o+e), -e, -o (host-computed, so they stay in SGPRs)
   const f16x2 NOE2 = as_f16x2(as_u16x2(a.f16_noe)), NE2 = as_f16x2(as_u16x2(a.f16_ne)),
               NO2 = as_f16x2(as_u16x2(a.f16_no));
-  // SKEW (skewed rows): cell (i, j) of a tile is held in the frame of its
-  // anti-diagonal k = (query row i) + (tile column j): H^ = H + c_k, T~ = G + c_k, c_k = e (k - 1).
-  // ct[k + 2] = c_k (both halves), read with scalar loads; row -1 and column -1 hold H = 0 as
-  // their frames' floors and a T~ far below every floor (-2048: it only ever enters a max)
+  // SKEW (skewed rows): cell (i, j) of a tile is held in the frame k = (query row i
+  // mod 8) + (tile column j), the anti-diagonal within a block of 8 rows: H^ = H + c_k, T~ = G +
+  // c_k, c_k = e (k - 1); every wave has the same frames.  ct[k + 2] = c_k (both halves), read
+  // with scalar loads; row -1 and column -1 hold H = 0 as their frames' floors and a T~ far below
+  // every floor (-2048: it only ever enters a max).  The running best is SWK_SKEW_ACC
+  // accumulators: bk[a] folds the rows r with (r mod 8) / 2 = a (gen_f16_rows.py)
   typedef __attribute__((address_space(4))) const uint32_t cst_u32;
   cst_u32* const ct = reinterpret_cast<cst_u32*>(reinterpret_cast<uintptr_t>(a.ctab));
   constexpr uint32_t SKEW_NEG = 0xBC00BC00u;
-  uint32_t skew_c0 = 0;  // c of this wave's row 0 in column -1 (frame wave R - 1)
-  if constexpr (SKEW) skew_c0 = ct[wave * R + 1];
-  // a tile's column -1: H = 0 in every row's frame (Hl[r] = c_{wave R + r - 1}), the diagonal
-  // above it, and the running best in the frame its first column's first step starts from
-  const auto skew_reset = [&](u16x2 (&H)[R], u16x2 (&X)[R], u16x2& bst, u16x2& pup) {
-    // (from an opaque copy: the 2R values are loop-invariant, and LLVM would otherwise keep
-    // them live across the column loop, R VGPRs spilled)
+  constexpr int NB = SKEW ? SWK_SKEW_ACC : 1;
+  static_assert(NB == 1 || NB == 4, "the generated rows fold into 4 accumulators");
+  uint32_t skew_c0 = 0;  // c of a block's row 0 in column -1 (frame -1)
+  if constexpr (SKEW) skew_c0 = ct[1];
+  // a tile's column -1: H = 0 in every row's frame (Hl[r] = c_{(r mod 8) - 1}), the diagonal
+  // above the wave's row 0 (row 7 of the block above: frame 6), and each accumulator at the floor
+  // of the frame it starts column 0 in (frame 2a; the last one a move before it, frame 5, since
+  // column 0's first block runs that move and folds column -1's class 7)
+  const auto skew_reset = [&](u16x2 (&H)[R], u16x2 (&X)[R], u16x2 (&bk)[NB], u16x2& pup) {
+    // (from an opaque copy: the values are loop-invariant, and LLVM would otherwise keep
+    // them live across the column loop, spilled)
     uint32_t c0 = skew_c0;
     asm volatile("" : "+v"(c0));
     f16x2 h = as_f16x2(__builtin_bit_cast(u16x2, c0));
     const f16x2 ne = as_f16x2(as_u16x2(a.f16_ne));
-    pup = as_u16x2(h + ne);
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-      H[r] = as_u16x2(h);
+      if (r < 8) {
+        H[r] = as_u16x2(h);
+        h = h - ne;
+      } else {
+        H[r] = H[r - 8];
+      }
       X[r] = __builtin_bit_cast(u16x2, SKEW_NEG);
-      h = h - ne;
     }
-    bst = H[R - 2];
+    pup = H[7];
+    if constexpr (NB == 4) {
+      bk[0] = H[1];
+      bk[1] = H[3];
+      bk[2] = H[5];
+      bk[3] = H[6];
+    }
   };
   (void)ct; (void)skew_reset;
   if (wave == 0) {
@@ -283,8 +326,9 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
     Xl[r] = X0;
   }
   u16x2 best = {0, 0};
+  u16x2 bk[NB] = {};  // SKEW: the accumulators of the running best
   u16x2 prevUpH = H0;  // H(row above, column -1)
-  if constexpr (SKEW) skew_reset(Hl, Xl, best, prevUpH);
+  if constexpr (SKEW) skew_reset(Hl, Xl, bk, prevUpH);
   uint2 rlo, rhi;      // raw codes of the next chunk (prefetched one phase ahead)
   load_raw<C, !MQ>(cur, vc0, vc0 < nfull, a.pad, packed, rlo, rhi);
   if (STREAM && threadIdx.x == 0) sq[W] = total;
@@ -334,9 +378,10 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
   // row is RS entries from the next, so a column's address is an instruction offset.
   const uint32_t pbase = (uint32_t)wave * R;
   const uint32_t padc = a.pad;
-  // BAL hand-off of one wave's column state {H, T of its R rows, the diagonal H above, best}
-  // at a head's end / a tail's start: word i of lane l at state[((g W + wave) (2R + 2) + i) 64
-  // + l] (coalesced), written and read with sc1 (write-through / L2) accesses and a flag
+  // BAL hand-off of one wave's column state {H, T of its R rows, the diagonal H above, best (SKEW:
+  // its accumulators)} at a head's end / a tail's start: word i of lane l at state[((g W + wave)
+  // BW + i) 64 + l], BW = SWK_BAL_WORDS (coalesced), written and read with sc1 (write-through /
+  // L2) accesses and a flag
   // (MI355X_MICROARCH.md, inter-workgroup visibility: sc1 stores, vmcnt(0), sc1 flag; sc1 poll,
   // sc1 loads).  The consumer's tail is its last visit and the producer's head its first, so
   // the flag is normally long set; the poll is bounded (poll_limit, about 4 s) and a time-out
@@ -345,11 +390,12 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
   // would otherwise hoist all 2R + 2 of them out of the phase loop, 2 VGPRs each, and spill;
   // with the copy taken of the finished base address instead, that base alone was hoisted and
   // spilled, 2 x 8 B of scratch per lane)
+  constexpr int BW = SWK_BAL_WORDS(R, NB);
   int bal_pend = 0;  // BAL: phases until the head's flag goes out (0: none pending)
   const auto bal_store = [&](int g_to) {
     uint32_t ol = (uint32_t)lane;
     asm volatile("" : "+v"(ol));
-    uint32_t* sp = a.bal_state + ((size_t)g_to * W + wave) * (2 * R + 2) * 64 + ol;
+    uint32_t* sp = a.bal_state + ((size_t)g_to * W + wave) * BW * 64 + ol;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       __hip_atomic_store(sp + r * 64, as_u32(Hl[r]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -357,8 +403,10 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
                          __HIP_MEMORY_SCOPE_AGENT);
     }
     __hip_atomic_store(sp + 2 * R * 64, as_u32(prevUpH), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(sp + (2 * R + 1) * 64, as_u32(best), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+    for (int i = 0; i < NB; ++i)
+      __hip_atomic_store(sp + (2 * R + 1 + i) * 64, as_u32(SKEW ? bk[i] : best), __ATOMIC_RELAXED,
+                         __HIP_MEMORY_SCOPE_AGENT);
     bal_pend = 2;  // the flag goes out a phase later, when the stores have long completed
   };
   const auto bal_flag_out = [&]() {
@@ -386,7 +434,7 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     uint32_t ol = (uint32_t)lane;
     asm volatile("" : "+v"(ol));
-    const uint32_t* sp = a.bal_state + ((size_t)blockIdx.x * W + wave) * (2 * R + 2) * 64 + ol;
+    const uint32_t* sp = a.bal_state + ((size_t)blockIdx.x * W + wave) * BW * 64 + ol;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       Hl[r] = as_u16x2(__hip_atomic_load(sp + r * 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
@@ -395,8 +443,13 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
     }
     prevUpH = as_u16x2(
         __hip_atomic_load(sp + 2 * R * 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    best = as_u16x2(
-        __hip_atomic_load(sp + (2 * R + 1) * 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+      const u16x2 v = as_u16x2(__hip_atomic_load(sp + (2 * R + 1 + i) * 64, __ATOMIC_RELAXED,
+                                                 __HIP_MEMORY_SCOPE_AGENT));
+      if constexpr (SKEW) bk[i] = v;
+      else best = v;
+    }
 #if SWK_STAMPS
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     st_bload += __builtin_amdgcn_s_memtime() - sb0;
@@ -476,8 +529,12 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
         else
           cur = lane_targets<!MQ>(a.res, a.offs, a.lens, n, ntile, lane, packed, idx, a.ulen,
                                   a.ustride);
-        tile_chunks<C>(cur, (size_t)ntile * SWB_TILE + lane, (size_t)ntile * SWB_TILE + lane + 64,
-                    n, nch_n, nfull_n, ncl_n);
+        if constexpr (SKEW)
+          tile_chunks_local<C>(cur, (size_t)ntile * SWB_TILE + lane,
+                               (size_t)ntile * SWB_TILE + lane + 64, n, lane, nch_n, nfull_n, ncl_n);
+        else
+          tile_chunks<C>(cur, (size_t)ntile * SWB_TILE + lane,
+                         (size_t)ntile * SWB_TILE + lane + 64, n, nch_n, nfull_n, ncl_n);
         if (BAL && nvend >= 0 && nvend < nch_n) ncl_n = C;
         if (BAL && nvend < 0) nvend = nch_n;
         load_raw<C, !MQ>(cur, nc0, nc0 < nfull_n, a.pad, STREAM ? packed_n : packed, rlo, rhi);
@@ -488,29 +545,35 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
         dma_edge_chunk<C>(a.edge_in + ((size_t)(last ? nunit : MQ ? unit : tile) * a.ecols +
                                     (size_t)(last ? 0 : c + 1) * C) * 64,
                        ein + (size_t)((g + 1) & 1) * C * RS, lane);
-      uint2* rin = wave > 0 ? ring + ((size_t)((wave - 1) * 2 + slot) * C) * RS + lane
-                   : seg_in ? ein + (size_t)slot * C * RS + lane
+      // (SKEW: from an opaque copy of the lane, as the other loop-invariant addresses; the
+      // skewed column has no VGPR to keep ring + lane in)
+      int rl = lane;
+      if constexpr (SKEW) asm volatile("" : "+v"(rl));
+      uint2* rin = wave > 0 ? ring + ((size_t)((wave - 1) * 2 + slot) * C) * RS + rl
+                   : seg_in ? ein + (size_t)slot * C * RS + rl
                             : ring + 64;
       // the last wave's sink: column jj's entry of the slot it reads was consumed a column
       // earlier (rv runs one column ahead), the producer writes the other slot in this phase
       // and refills this one only after the phase barrier
-      uint2* rout = wave < W - 1 ? ring + ((size_t)(wave * 2 + slot) * C) * RS + lane
+      uint2* rout = wave < W - 1 ? ring + ((size_t)(wave * 2 + slot) * C) * RS + rl
                     : W > 1      ? rin
-                                 : ring + lane;
-      // SKEW: the floors of this chunk-phase's frames, cs[s] = c_k for k = wave R + 8 c - 1 + s
-      // (row r of column jj: s = r + jj + 1), wave-uniform, read into SGPRs.  Wave 0 has no wave
-      // above it: its row -1 holds H = 0 in a frame that moves with the column, so it rewrites
-      // the boundary entries of the 8 column rows before it reads them (the same wave's LDS
-      // accesses stay in order)
+                                 : ring + rl;
+      // SKEW: the floors of this chunk-phase's frames, cs[s] = c_k for k = 8 c + s (row r of
+      // column jj: s = (r mod 8) + jj), the same for every wave, read into SGPRs.  Wave 0 has no
+      // wave above it: its row -1 holds H = 0 in the frame of a block's row 7, which moves with
+      // the column, so it rewrites the boundary entries of the 8 column rows before it reads
+      // them (the same wave's LDS accesses stay in order).  Their T~ = -2048 becomes -2048 - 8e
+      // by the shift of row 0: exact (a multiple of 8 above -4096) and below A - o >= -2048,
+      // beside which alone it enters a max
       const int cu = __builtin_amdgcn_readfirstlane(c);
-      uint32_t cs[SKEW ? R + C : 1];
+      uint32_t cs[SKEW ? 7 + C : 1];
       if constexpr (SKEW) {
-        cst_u32* const sl = ct + (wave * R + cu * C + 1);
+        cst_u32* const sl = ct + (cu * C + 2);
 #pragma unroll
-        for (int s = 0; s < R + C; ++s) cs[s] = sl[s];
+        for (int s = 0; s < 7 + C; ++s) cs[s] = sl[s];
         if (wave == 0 && lane == 0) {
 #pragma unroll
-          for (int jj = 0; jj < C; ++jj) ring[jj * RS + 64] = make_uint2(cs[jj], SKEW_NEG);
+          for (int jj = 0; jj < C; ++jj) ring[jj * RS + 64] = make_uint2(cs[jj + 7], SKEW_NEG);
         }
       }
       (void)cu; (void)cs;
@@ -585,60 +648,60 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
             column_merged<R, RB, false>(lk, diag, upX, Hl, Xl, best, S2, O2, E2);
           }
         } else if constexpr (PAIR && SKEW) {
-          // the skewed rows (scripts/gen_f16_rows.py, skew_pair_block): 5 VALU per row; the
-          // table words hold s + 2e, row r's floor is cs[r + jj + 1]
+          // the skewed rows (scripts/gen_f16_rows.py, skew_pair_block): 4.75 VALU per row; the
+          // table words hold s + 2e (a block's first row: s + 2e - 8e), row r's floor is
+          // cs[(r mod 8) + jj]; the folds of the best sit in the last block, the last
+          // accumulator's second half in the next column's first block
           const uint32_t nwl = jj + 1 < C ? (jj + 1 < 4 ? clo.x : clo.y) : rlo.x;
           const uint32_t nwh = jj + 1 < C ? (jj + 1 < 4 ? chi.x : chi.y) : rhi.x;
           const int nsh = jj + 1 < C ? 8 * ((jj + 1) & 3) : 0;
           uint32_t Da, Db, AO;
-          const uint32_t no = as_u32(as_u16x2(NO2)), e2 = a.f16_e2, e2f = a.f16_e2f;
-          u16x2 bst = best;
-#define SWK_SKEW_OUT(B, DA)                                                                   \
+          const uint32_t no = as_u32(as_u16x2(NO2)), e1 = a.f16_e1, ne8 = a.f16_ne8;
+#define SWK_SKEW_OUT(B, DA, DB)                                                               \
   [h0] "+v"(Hl[B]), [h1] "+v"(Hl[B + 1]), [h2] "+v"(Hl[B + 2]), [h3] "+v"(Hl[B + 3]),          \
       [h4] "+v"(Hl[B + 4]), [h5] "+v"(Hl[B + 5]), [h6] "+v"(Hl[B + 6]), [h7] "+v"(Hl[B + 7]),  \
       [t0] "+v"(Xl[B]), [t1] "+v"(Xl[B + 1]), [t2] "+v"(Xl[B + 2]), [t3] "+v"(Xl[B + 3]),      \
       [t4] "+v"(Xl[B + 4]), [t5] "+v"(Xl[B + 5]), [t6] "+v"(Xl[B + 6]), [t7] "+v"(Xl[B + 7]),  \
-      [Db] "=&v"(Db), [best] "+v"(bst), [Da] DA(Da), [AO] DA(AO)
-#define SWK_SKEW_IN(B, P0, P1)                                                                \
+      [Db] DB(Db), [Da] DA(Da), [AO] DA(AO)
+#define SWK_SKEW_IN(P0, P1)                                                                   \
   [p0] "v"(P0.x), [p1] "v"(P0.y), [p2] "v"(P0.z), [p3] "v"(P0.w), [p4] "v"(P1.x),             \
-      [p5] "v"(P1.y), [p6] "v"(P1.z), [p7] "v"(P1.w), [no] "s"(no), [e2] "s"(e2),             \
-      [c0] "s"(cs[B + jj + 1]), [c1] "s"(cs[B + jj + 2]), [c2] "s"(cs[B + jj + 3]),           \
-      [c3] "s"(cs[B + jj + 4]), [c4] "s"(cs[B + jj + 5]), [c5] "s"(cs[B + jj + 6]),           \
-      [c6] "s"(cs[B + jj + 7]), [c7] "s"(cs[B + jj + 8])
-#define SWK_SKEW_BLOCK(KIND, B, P0, P1)                                                       \
-  if constexpr (KIND == 0)                                                                    \
-    asm volatile(SWK_F16SKEW_F : SWK_SKEW_OUT(B, "=&v")                                       \
-                 : SWK_SKEW_IN(B, P0, P1), [e2f] "s"(e2f), [up] "v"(upX), [dg] "v"(diag),     \
-                   [pw] "v"(pw));                                                             \
-  else if constexpr (KIND == 1)                                                               \
-    asm volatile(SWK_F16SKEW_M : SWK_SKEW_OUT(B, "+v") : SWK_SKEW_IN(B, P0, P1),              \
-                 [up] "v"(Xl[B - 1]));                                                        \
-  else                                                                                        \
-    asm volatile(SWK_F16SKEW_L : SWK_SKEW_OUT(B, "+v") : SWK_SKEW_IN(B, P0, P1),              \
-                 [up] "v"(Xl[B - 1]));
+      [p5] "v"(P1.y), [p6] "v"(P1.z), [p7] "v"(P1.w), [no] "s"(no), [ne8] "s"(ne8),           \
+      [c0] "s"(cs[jj]), [c1] "s"(cs[jj + 1]), [c2] "s"(cs[jj + 2]), [c3] "s"(cs[jj + 3]),     \
+      [c4] "s"(cs[jj + 4]), [c5] "s"(cs[jj + 5]), [c6] "s"(cs[jj + 6]), [c7] "s"(cs[jj + 7])
+// rows B .. B + 6 of the blocks above the last one, for its folds (class 7 is folded by the
+// next column's first block)
+#define SWK_SKEW_FOLD(N, B)                                                                   \
+  [N##0] "v"(Hl[B]), [N##1] "v"(Hl[B + 1]), [N##2] "v"(Hl[B + 2]), [N##3] "v"(Hl[B + 3]),     \
+      [N##4] "v"(Hl[B + 4]), [N##5] "v"(Hl[B + 5]), [N##6] "v"(Hl[B + 6])
           // (the table words one block ahead, as in the unskewed column below)
           uint4 pB0 = ld4(acur + 48), pB1 = ld4(acur + 64);  // block 1
           __builtin_amdgcn_sched_barrier(0);
-          SWK_SKEW_BLOCK(0, 0, pA0, pA1)
+          asm volatile(SWK_F16SKEW_F
+                       : SWK_SKEW_OUT(0, "=&v", "=&v"), [up] "+v"(upX), [b3] "+v"(bk[3])
+                       : SWK_SKEW_IN(pA0, pA1), [e1] "s"(e1), [dg] "v"(diag), [pw] "v"(pw),
+                         [x] "v"(Hl[15]), [y] "v"(Hl[23]), [z] "v"(Hl[31]));
           pA0 = ld4(acur + 80);  // block 2
           pA1 = ld4(acur + 96);
           __builtin_amdgcn_sched_barrier(0);
-          SWK_SKEW_BLOCK(1, 8, pB0, pB1)
+          asm volatile(SWK_F16SKEW_M : SWK_SKEW_OUT(8, "+v", "+v") : SWK_SKEW_IN(pB0, pB1));
           pB0 = ld4(acur + 112);  // block 3
           pB1 = ld4(acur + 128);
           __builtin_amdgcn_sched_barrier(0);
-          SWK_SKEW_BLOCK(1, 16, pA0, pA1)
+          asm volatile(SWK_F16SKEW_M : SWK_SKEW_OUT(16, "+v", "+v") : SWK_SKEW_IN(pA0, pA1));
           acur = pair_addr(nwl, nwh, nsh);  // next column: block 0 and row-0 word
           pA0 = ld4(acur + 16);
           pA1 = ld4(acur + 32);
           pw = ld1(acur + 12);
           __builtin_amdgcn_sched_barrier(0);
-          SWK_SKEW_BLOCK(2, R - 8, pB0, pB1)
-#undef SWK_SKEW_BLOCK
+          asm volatile(SWK_F16SKEW_L
+                       : SWK_SKEW_OUT(R - 8, "+v", "+v"), [b0] "+v"(bk[0]), [b1] "+v"(bk[1]),
+                         [b2] "+v"(bk[2]), [b3] "+v"(bk[3])
+                       : SWK_SKEW_IN(pB0, pB1), [e1] "s"(e1), SWK_SKEW_FOLD(g, 0),
+                         SWK_SKEW_FOLD(k, 8), SWK_SKEW_FOLD(m, 16));
+#undef SWK_SKEW_FOLD
 #undef SWK_SKEW_OUT
 #undef SWK_SKEW_IN
-          (void)Db; (void)AO;
-          best = bst;
+          (void)Db; (void)AO; (void)Da;
           upX = Xl[R - 1];
         } else if constexpr (PAIR) {
           // the next column's table address (its codes: this chunk, or byte 0 of the next)
@@ -737,7 +800,7 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
         }
         // pin the running max once per column: otherwise LLVM re-associates the max over the
         // whole phase into a tree and keeps every M live
-        asm volatile("" : "+v"(best));
+        if constexpr (!SKEW) asm volatile("" : "+v"(best));
         rout[jj * RS] = make_uint2(as_u32(Hl[R - 1]), as_u32(upX));
       }
       if constexpr (PAIR && TRIM) {
@@ -760,14 +823,18 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
           bal_store((int)blockIdx.x + 1);
         } else {  // this wave's part of tile k is done
         if constexpr (SKEW) {
-          // the odd rows of the tile's last column (no later column pairs them), then out of
-          // the frame the best ends in: that of this wave's last row in the last column
-          f16x2 bb = as_f16x2(best);
-          const f16x2 e2 = as_f16x2(as_u16x2(a.f16_e2)), e2f = as_f16x2(as_u16x2(a.f16_e2f));
-#pragma unroll
-          for (int r = 1; r < R; r += 2) bb = fmax2(bb + (r == 1 ? e2f : e2), as_f16x2(Hl[r]));
-          const uint32_t cf =
-              ct[__builtin_amdgcn_readfirstlane(wave * R + R + 1 + cu * C + ncols - 1)];
+          // the last accumulator's move and class 7 of the tile's last column (no later column
+          // runs them), then every accumulator into that frame, 7 + the last column, and out
+          // of it: accumulator a ends the column in frame 2a + 1 + column
+          // (each two frames on as two adds of e, an SGPR operand: a constant 2e would be
+          // loop-invariant and live, a VGPR, across the column loop)
+          const f16x2 e1 = as_f16x2(as_u16x2(a.f16_e1));
+          f16x2 bb = fmax2(fmax2(as_f16x2(bk[3]) + e1, as_f16x2(Hl[7])), as_f16x2(Hl[15]));
+          bb = fmax2(fmax2(bb, as_f16x2(Hl[23])), as_f16x2(Hl[31]));
+          f16x2 lo = fmax2((as_f16x2(bk[0]) + e1) + e1, as_f16x2(bk[1]));
+          lo = fmax2((lo + e1) + e1, as_f16x2(bk[2]));
+          bb = fmax2((lo + e1) + e1, bb);
+          const uint32_t cf = ct[__builtin_amdgcn_readfirstlane(cu * C + ncols + 8)];
           best = as_u16x2(bb - as_f16x2(__builtin_bit_cast(u16x2, cf)));
         }
         uint32_t* bs = bestsh + (k % W) * SWB_TILE;
@@ -817,7 +884,7 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
         }
         best = (u16x2){0, 0};
         prevUpH = H0;
-        if constexpr (SKEW) skew_reset(Hl, Xl, best, prevUpH);
+        if constexpr (SKEW) skew_reset(Hl, Xl, bk, prevUpH);
         tile = ntile;
         if constexpr (STREAM) {
           packed = packed_n;
@@ -929,11 +996,12 @@ static hipError_t launch_score(const ScoreArgs& a, int W, uint32_t prof_bytes, h
   return hipGetLastError();
 }
 
-// The SKEW variants' arguments: the floor table and the running best's two frame steps.
-static void skew_args(ScoreArgs& a, const uint32_t* tab, int R) {
+// The SKEW variants' arguments: the floor table, an accumulator's frame step and the shift of
+// a block's first row.
+static void skew_args(ScoreArgs& a, const uint32_t* tab) {
   a.ctab = tab;
-  a.f16_e2 = f16_pair(2 * (int)a.E);
-  a.f16_e2f = f16_pair((3 - R) * (int)a.E);
+  a.f16_e1 = f16_pair((int)a.E);
+  a.f16_ne8 = f16_pair(-8 * (int)a.E);
 }
 
 }  // namespace swk
@@ -1009,7 +1077,7 @@ extern "C" hipError_t swk_launch_score(int R, int RB, int col0, int prof, int go
     if (skew_tab && (R != 32 || !f16 || prof || gotoh || col0 || edge_in || edge_out || W > 4))
       return hipErrorInvalidValue;
     if (skew_tab) {
-      swk::skew_args(a, skew_tab, 32);
+      swk::skew_args(a, skew_tab);
       return swk::launch_score<32, 4, false, false, false, true, true, false, false, 8, false,
                                false, true>(a, W, 0, st);
     }
@@ -1050,7 +1118,7 @@ extern "C" void swk_set_stamps(void* p) { swk::g_stamps_host = static_cast<uint6
 // Balanced chunk ranges (ScoreArgs.bal_*) for the DNA merged f16 pair-table kernel (the
 // headline shape): codes one byte each (or ustride / ulen), one query segment of W <= 4 waves.
 // swk_bal_slots gives the grid (every resident slot); the host sizes bal_state ((grid + 1) x W
-// x (2R + 2) x 64 words) and bal_flag ((grid + 1) x W words, zeroed once); a hand-off wait
+// x SWK_BAL_WORDS x 64 words) and bal_flag ((grid + 1) x W words, zeroed once); a hand-off wait
 // that runs out after poll_limit polls marks *fault (SWK_FAULT_BAL).  plan: grid + 1 entries {tile, chunk, chunk index} (swk_bal_plan_uniform for
 // a uniform batch; a ragged batch visited longest first through the device sort's permutation
 // idx / nidx / ident passes the sort's, swk_sort_lens with the same grid).
@@ -1130,7 +1198,7 @@ extern "C" hipError_t swk_launch_pair_bal(const uint8_t* res, const uint64_t* of
   a.stall = stall;
   a.sidx = sidx;
   if (skew_tab) {  // the skewed rows (qtab holds s + 2e)
-    swk::skew_args(a, skew_tab, 32);
+    swk::skew_args(a, skew_tab);
     if (trim)
       return swk::launch_score<32, 4, false, false, false, true, true, false, false, 8, true, true,
                                true>(a, W, 0, st, grid);

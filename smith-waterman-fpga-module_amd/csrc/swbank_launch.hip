@@ -138,10 +138,12 @@ sw_status launch(sw_bank* b, const uint8_t* d_res, const uint64_t* d_offs,
   const char* arith = opt16 ? "f16+u16-rescore" : use_f16 ? "f16" : "u16";
   // the f16 pass of the tile kernel reads the letter-pair table when the query has one
   const bool use_pair = use_f16 && b->pair_bytes != 0 && env_int("SWBANK_PAIR", 1) != 0;
-  // The skewed rows of the merged pair kernel (DESIGN 3.1, 5 VALU per row instead of 5.5):
-  // every cell carries its anti-diagonal's offset e (k - 1), k < rows + cols, on top of its
-  // value, so the exact range must hold both: max(s) min(|q|, L) + max(s) + e (rows + cols) <=
-  // 2048 and the most negative intermediate >= -2048.  rows: the workgroup's (the query padded
+  // The skewed rows of the merged pair kernel (DESIGN 3.1, 4.75 VALU per row instead of 5.5):
+  // every cell carries its frame's offset e (k - 1) on top of its value, so the exact range
+  // must hold both.  The frames restart every 8 rows, k < 8 + cols, and need less than this
+  // bound grants; it is kept as it was when k ran over all rows, k < rows + cols (the same
+  // batches take these rows as before): max(s) min(|q|, L) + max(s) + e (rows + cols) <= 2048
+  // and the most negative intermediate >= -2048.  rows: the workgroup's (the query padded
   // to whole waves); cols: the columns a tile runs, max_len rounded up to the 8-column chunk
   // (only the trimmed kernel stops at a tile's last code: the frames, the running best and the
   // unshift of the others go on through the last chunk's padding).  Past that bound nothing
@@ -153,7 +155,7 @@ sw_status launch(sw_bank* b, const uint8_t* d_res, const uint64_t* d_offs,
       exact16 && use_pair && !gotoh && nseg == 1 && b->skew_entries != 0 && wait_prev &&
       (packed == SWK_PACK_BYTES || packed == SWK_PACK_NIBBLE) &&
       top + (uint64_t)b->E * ((uint64_t)b->segs[0].W * b->R + skew_cols) <= 2048u &&
-      b->skew_neg >= -2048 && skew_cols + 136 <= b->skew_entries &&
+      b->skew_neg >= -2048 && skew_cols + 16 <= b->skew_entries &&
       env_int("SWBANK_SKEW", 1) != 0;
   bool wave_fb = false;  // the wave kernel re-scores its own flagged pairs
   if (use_wave) {
@@ -431,7 +433,7 @@ sw_status launch(sw_bank* b, const uint8_t* d_res, const uint64_t* d_offs,
         uint32_t* fw = fault_word(b);
         if (!fw) return fail(b, SW_ERR_NOMEM, "fault word allocation failed");
         if (grid && (rbal || ntiles >= 2 * (size_t)grid)) {
-          const size_t sw = (size_t)(grid + 1) * Wl * (2 * 32 + 2) * 64;
+          const size_t sw = (size_t)(grid + 1) * Wl * SWK_BAL_WORDS(32, SWK_SKEW_ACC) * 64;
           HIPOK(b, b->bal_state.reserve(sw));
           if (b->bal_flag.cap < (size_t)(grid + 1) * Wl) {  // zeroed once: flags carry bal_gen
             HIPOK(b, b->bal_flag.reserve((size_t)(grid + 1) * Wl));
