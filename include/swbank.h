@@ -28,6 +28,13 @@
  *   sw_top_hits / sw_top_hits_device
  *       ≙ the "The best scores are:" list ssearch36 prints over the bank's scores (the
  *         reference's data/alignments500.txt): the k best, highest score first.
+ *   sw_align_hits / sw_align_set_hits (and their _device forms)
+ *       ≙ the per-hit report ssearch36 prints below that list (data/alignments500.txt:
+ *         score, identity, overlap coordinates and the alignment), for one query and, applied
+ *         once per query, for a query set.
+ *   sw_best_queries / sw_best_queries_device
+ *       ≙ the same "best scores" question asked per target of a query set: which query hits
+ *         this target best (the read-mapping shape, where the reads are the batch).
  *   sw_encode_ascii
  *       ≙ ConvertToBase (ScoreBank_v1_tb.sv:44-52): A=2 G=3 T=0 C=1 (lower case too);
  *         any other byte -> SW_DNA_N (4), which mismatches every code.
@@ -68,10 +75,13 @@ extern "C" {
  * ABI 6 additions (purely additive, the version stays 6; test SWBANK_HAS_ALIGN): alignments of
  *        chosen hits -- sw_alignment, sw_align_hits, sw_align_hits_device, sw_cigar_string;
  *        (test SWBANK_HAS_TOPK) the k best hits of a score matrix -- sw_top_hits,
- *        sw_top_hits_device. */
+ *        sw_top_hits_device; (test SWBANK_HAS_ALIGN_SET) alignments against a query set --
+ *        sw_align_set_hits, sw_align_set_hits_device, SW_QUERY_NONE, SW_ALIGN_NO_HIT -- and the
+ *        best query of every target -- sw_best_queries, sw_best_queries_device. */
 #define SWBANK_ABI_VERSION 6
 #define SWBANK_HAS_ALIGN 1
 #define SWBANK_HAS_TOPK 1
+#define SWBANK_HAS_ALIGN_SET 1
 
 typedef int32_t sw_status;
 enum {
@@ -321,6 +331,38 @@ sw_status sw_top_hits(sw_bank *bank, const int32_t *scores, const uint64_t *ids,
                       size_t n, size_t nq, size_t k, int32_t min_score,
                       uint64_t *hits, int32_t *hit_scores, uint64_t *hit_ids, uint32_t *counts);
 
+/* ---- the best query per target (ABI 6 addition) ---------------------------------------------
+ * The column maximum of the nq x n score matrix of a query set: for every target, which query
+ * hits it best.  It is what "The best scores are:" of ssearch36 (the reference's
+ * data/alignments500.txt) answers when the roles are swapped: in read mapping the references are
+ * the query set and the reads are the batch, and the caller asks where each read belongs.
+ * sw_score_batch_device (a set), sw_best_queries_device and sw_align_set_hits_device
+ * (d_hit_queries = d_best_query, d_hits = NULL) run back to back on one stream with no host
+ * round trip.
+ *
+ * For every target k < n: best_query[k] is the lowest i < nq whose scores[i*n + k] is the
+ * column's maximum, best_score[k] that maximum; if the maximum is < min_score (INT32_MIN: no
+ * threshold) they are SW_QUERY_NONE and INT32_MIN.  Either output may be NULL, not both.  Any
+ * int32 is a legal score; the result is bitwise identical from run to run.
+ * SW_ERR_ARG (nothing is written): a NULL bank or scores, or both outputs NULL; n or nq == 0;
+ * nq > 65536 (the limit of sw_load_queries); n > 2^32; nq * n overflowing size_t. */
+#define SW_QUERY_NONE UINT32_MAX       /* "no query" in a hit-query list */
+
+/* Device buffers, asynchronous on `stream` (NULL = the bank's).  Like sw_top_hits_device it
+ * consults neither the penalties nor the loaded queries, returns a latched hand-off fault of an
+ * earlier device call, runs on the root device of a multi-device bank, and orders its use of
+ * the bank's scratch after the previous call's, so calls on different streams need no
+ * synchronisation between them.  sw_last_kernel reports "best-query nq=<nq> n=<n>"; with
+ * sw_bank_set_timing the call is bracketed as one launch. */
+sw_status sw_best_queries_device(sw_bank *bank, const int32_t *d_scores, size_t n, size_t nq,
+                                 int32_t min_score, uint32_t *d_best_query,
+                                 int32_t *d_best_score, void *stream);
+
+/* Host buffers, blocking: uploads the scores, runs the same kernel, copies the result back.
+ * Not counted in sw_counters.h2d_bytes. */
+sw_status sw_best_queries(sw_bank *bank, const int32_t *scores, size_t n, size_t nq,
+                          int32_t min_score, uint32_t *best_query, int32_t *best_score);
+
 /* ---- alignments of chosen hits (ABI 6 addition) -------------------------------------------
  * The score calls return a number per pair; these return, for a caller-chosen list of hits
  * (typically the best few dozen to few thousand of a batch), where the alignment lies and the
@@ -348,7 +390,7 @@ sw_status sw_top_hits(sw_bank *bank, const int32_t *scores, const uint64_t *ids,
  * A record with SW_ALIGN_NO_PATH has exact coordinates, no ops, and n_columns = n_identities = 0.
  *
  * Status: SW_ERR_STATE without penalties or a query, or while a query set of more than one
- * query is loaded; SW_ERR_UNSUPPORTED for SW_GAP_MERGED penalties whose largest substitution
+ * query is loaded (sw_align_set_hits below takes the set); SW_ERR_UNSUPPORTED for SW_GAP_MERGED penalties whose largest substitution
  * score exceeds open + extend (the only case in which the HDL's first-column rule,
  * SW_ProcessingElement_v1.0.v:131-141, changes a score: the reversed pass cannot apply it); a
  * latched hand-off fault of an earlier device call is returned as by the other device calls.
@@ -400,6 +442,53 @@ sw_status sw_align_hits(sw_bank *bank, const uint8_t *residues, size_t residues_
                         const uint64_t *offsets, const uint32_t *lens, const uint64_t *ids,
                         size_t n, const uint64_t *hits, size_t n_hits, sw_alignment *out,
                         uint32_t *cigar, size_t cigar_cap, size_t *cigar_used);
+
+/* ---- alignments of chosen hits against a query set (ABI 6 addition) -------------------------
+ * sw_align_hits[_device] for the pairs of a query set (sw_load_queries): ssearch36's per-hit
+ * report (data/alignments500.txt) applied once per query of the set.  Apart from the pair list
+ * a call behaves exactly as its single-query counterpart above: the score, the end / start /
+ * CIGAR rules, the empty pair, SW_ALIGN_NO_PATH, the SWBANK_ALIGN_MB budget and its chunks, the
+ * cigar_offset = h * cigar_stride layout of the device call and the packed layout of the host
+ * call, SW_ERR_UNSUPPORTED for merged penalties with max(s) > open + extend, the latched
+ * hand-off fault, the multi-device bank running on its root.  nq = sw_query_count(bank); a bank
+ * with one loaded query is a set of one, and the call then equals sw_align_hits[_device] record
+ * for record and op for op.  SW_ERR_STATE without penalties or a query.
+ *
+ * The pair list:
+ *   query   of hit h: hit_queries[h] if hit_queries is given (hits_per_query must then be 0);
+ *           else h / hits_per_query -- the nq x k layout sw_top_hits_device writes, with
+ *           hits_per_query = that call's k; then hits_per_query >= 1 and
+ *           n_hits <= nq * hits_per_query.  Both given, or neither: SW_ERR_ARG.
+ *   target  of hit h: hits[h] if hits is given; else h itself (n_hits <= n) -- the form that
+ *           follows sw_best_queries_device, whose output holds one entry per target.
+ *   no pair a hit whose query is SW_QUERY_NONE or whose target is SW_HIT_NONE (the sentinel tails
+ *           of sw_top_hits_device, the thresholded output of sw_best_queries_device): its record
+ *           is index = id = SW_HIT_NONE, score 0, flags SW_ALIGN_EMPTY | SW_ALIGN_NO_HIT, every
+ *           coordinate and count 0, cigar_len 0 (cigar_offset as for every record of the call);
+ *           nothing of the batch is read for it.  Every record of the call is fully defined.
+ *   record  out[h] belongs to hit h; it has no query field (the caller knows hit h's query);
+ *           index and id speak of the target.
+ * The device call validates nothing it would have to read back; a query index >= nq or a target
+ * >= n in its lists is treated as naming no pair.  It sizes the direction-store slots from
+ * max_len x the longest query of the set.  The host call returns SW_ERR_ARG for a query index
+ * >= nq or a target >= n other than the sentinels, checks the batch as sw_align_hits does, and
+ * sizes its chunks from the hits' actual windows.  sw_last_kernel reports
+ * "align-set i32 nq=<nq> hits=<n_hits> chunks=<c>"; with sw_bank_set_timing the end / start
+ * passes and the path passes are bracketed as one launch each. */
+enum { SW_ALIGN_NO_HIT = 4 };  /* flag: the slot named no pair (always with SW_ALIGN_EMPTY) */
+
+sw_status sw_align_set_hits_device(sw_bank *bank, const uint8_t *d_residues,
+                                   const uint64_t *d_offsets, const uint32_t *d_lens,
+                                   const uint64_t *d_ids, size_t n, uint32_t max_len,
+                                   const uint32_t *d_hit_queries, size_t hits_per_query,
+                                   const uint64_t *d_hits, size_t n_hits, sw_alignment *d_out,
+                                   uint32_t *d_cigar, uint32_t cigar_stride, void *stream);
+
+sw_status sw_align_set_hits(sw_bank *bank, const uint8_t *residues, size_t residues_len,
+                            const uint64_t *offsets, const uint32_t *lens, const uint64_t *ids,
+                            size_t n, const uint32_t *hit_queries, size_t hits_per_query,
+                            const uint64_t *hits, size_t n_hits, sw_alignment *out,
+                            uint32_t *cigar, size_t cigar_cap, size_t *cigar_used);
 
 /* ---- profiling (≙ the CAPI AFU's cycle counters, capi_sample_aligner/hdl-verliog/afu.v
  *      _DEBUGGING_ "calculation #N completed, runtime: C cycles") ------------------------- */

@@ -9,7 +9,10 @@
 
 /* One call's arguments: the batch, the hit list (hits == NULL: hit h is target h), the query's
  * codes and the alpha x alpha matrix on the device, the records and the CIGAR buffer (cigar_stride
- * 0: coordinates only), per-wave scratch rows (waves x 2 x scols x 8 B; scols >= every length). */
+ * 0: coordinates only), per-wave scratch rows (waves x 2 x scols x 8 B; scols >= every length).
+ * set != 0 (sw_align_set_hits*): hit h aligns query hit_queries[h], or h / hits_per_query, of
+ * the nq queries whose codes lie at query + qtab[i].x, qtab[i].y of them; a hit whose query is
+ * >= nq or whose target is >= n names no pair (SW_ALIGN_NO_HIT).  qlen is the longest query. */
 typedef struct SwkAlign {
   int gotoh;
   const uint8_t* res;
@@ -30,6 +33,12 @@ typedef struct SwkAlign {
   void* scratch;
   uint32_t scols;
   size_t waves; /* a multiple of 4 */
+  int set;
+  size_t n;                    /* targets in the batch (set) */
+  const uint2* qtab;           /* {offset, length} per query (set) */
+  uint32_t nq;
+  const uint32_t* hit_queries; /* or NULL: hits_per_query >= 1 */
+  uint32_t hits_per_query;
 } SwkAlign;
 
 /* Where one hit's window sits in the direction store (dwords) and its ops in the CIGAR buffer. */

@@ -1,6 +1,8 @@
 // swbank_align.hip — alignments of chosen hits (include/swbank.h "alignments of chosen hits",
-// DESIGN.md §3.9): the two ABI entries, the chunking of the direction store, the host call's
-// staging.  The kernels are in swbank_kalign.hip.
+// DESIGN.md §3.9): the ABI entries for one query (sw_align_hits*) and for a query set
+// (sw_align_set_hits*), the chunking of the direction store, the host calls' staging.  Both pairs
+// of entries run the same code; they differ in the pair list.  The kernels are in
+// swbank_kalign.hip.
 #include "swbank_bank.h"
 
 namespace {
@@ -10,28 +12,56 @@ uint64_t dir_budget() {
   return ((uint64_t)std::max(1, env_int("SWBANK_ALIGN_MB", 256)) << 20) / 4;
 }
 
-// The query's codes and the matrix on the device, built on first use per (penalties, query)
-// and uploaded on the bank stream like the other query tables (prepare_i32).
+// The pair list of a call.  !set (sw_align_hits*): hit h is the loaded query against target
+// hits[h].  set (sw_align_set_hits*): query hit_queries[h], or h / hits_per_query, against target
+// hits[h], or h.
+struct Pairs {
+  bool set;
+  const uint32_t* hit_queries;
+  size_t hits_per_query;
+  const uint64_t* hits;
+  size_t n_hits;
+};
+
+size_t query_count(const sw_bank* b) { return b->qset.size() > 1 ? b->qset.size() : 1; }
+
+// The queries' codes and the matrix on the device, built on first use per (penalties, queries)
+// and uploaded on the bank stream like the other query tables (prepare_i32): a {offset, length}
+// entry per query, the alpha x alpha matrix, then the codes of every query back to back.
 sw_status prepare_align(sw_bank* b) {
   if (b->al_ready) return SW_OK;
-  const size_t ql = b->query.size(), ml = b->matrix.size();
+  const size_t nq = query_count(b), ml = b->matrix.size();
+  size_t ql = 0;
+  for (size_t i = 0; i < nq; ++i) ql += (nq > 1 ? b->qset[i] : b->query).size();
+  if (ql > 0xFFFFFFFFull)
+    return fail(b, SW_ERR_UNSUPPORTED, "alignments: the query set holds more than 2^32 codes");
+  const size_t bytes = nq * sizeof(uint2) + ml + ql;
   HIPOK(b, hipEventSynchronize(b->ev_ready));  // the staging buffer is free again
-  HIPOK(b, b->stage.reserve(ql + ml));
-  HIPOK(b, b->al_tab.reserve(ql + ml));
+  HIPOK(b, b->stage.reserve(bytes));
+  HIPOK(b, b->al_tab.reserve(bytes));
   HIPOK(b, hipStreamWaitEvent(b->stream, b->ev_used, 0));
-  if (ql) std::memcpy(b->stage.p, b->query.data(), ql);
-  std::memcpy(b->stage.p + ql, b->matrix.data(), ml);
-  HIPOK(b, hipMemcpyAsync(b->al_tab.p, b->stage.p, ql + ml, hipMemcpyHostToDevice, b->stream));
+  uint8_t* codes = b->stage.p + nq * sizeof(uint2) + ml;
+  size_t at = 0;
+  for (size_t i = 0; i < nq; ++i) {
+    const std::vector<uint8_t>& q = nq > 1 ? b->qset[i] : b->query;
+    const uint2 e = make_uint2((uint32_t)at, (uint32_t)q.size());
+    std::memcpy(b->stage.p + i * sizeof(uint2), &e, sizeof(e));
+    if (!q.empty()) std::memcpy(codes + at, q.data(), q.size());
+    at += q.size();
+  }
+  std::memcpy(b->stage.p + nq * sizeof(uint2), b->matrix.data(), ml);
+  HIPOK(b, hipMemcpyAsync(b->al_tab.p, b->stage.p, bytes, hipMemcpyHostToDevice, b->stream));
   HIPOK(b, hipEventRecord(b->ev_ready, b->stream));
   b->al_ready = true;
   return SW_OK;
 }
 
-// The state both entries need; on return the bank is prepare()d.
-sw_status align_ready(sw_bank* b) {
+// The state every entry needs; on return the bank is prepare()d.  The single-query entries
+// refuse a loaded set.
+sw_status align_ready(sw_bank* b, bool set) {
   if (!b->have_pen || !b->have_query)
     return fail(b, SW_ERR_STATE, "penalties or query not loaded");
-  if (b->qset.size() > 1)
+  if (!set && b->qset.size() > 1)
     return fail(b, SW_ERR_STATE, "a query set is loaded: alignments take one query");
   const sw_status st = prepare(b);
   if (st != SW_OK) return st;
@@ -43,17 +73,36 @@ sw_status align_ready(sw_bank* b) {
   return prepare_align(b);
 }
 
+// What a set call's pair list must satisfy whatever its buffers hold; n targets in the batch.
+sw_status check_pairs(sw_bank* b, const Pairs& pr, size_t n) {
+  if (pr.n_hits > 0xFFFFFFFFull) return fail(b, SW_ERR_ARG, "hit lists hold < 2^32 hits");
+  if (!pr.set) return SW_OK;
+  const size_t nq = query_count(b);
+  if ((pr.hit_queries != nullptr) == (pr.hits_per_query != 0))
+    return fail(b, SW_ERR_ARG, "give hit_queries or hits_per_query >= 1, not both");
+  if (pr.hits_per_query > 0xFFFFFFFFull ||
+      (pr.hits_per_query && (pr.n_hits + pr.hits_per_query - 1) / pr.hits_per_query > nq))
+    return fail(b, SW_ERR_ARG, "n_hits = %zu > nq x hits_per_query = %zu x %zu", pr.n_hits, nq,
+                pr.hits_per_query);
+  if (!pr.hits && pr.n_hits > n)
+    return fail(b, SW_ERR_ARG, "no hit list: n_hits = %zu > n = %zu", pr.n_hits, n);
+  return SW_OK;
+}
+
 // The launch block of a call over `nh` hits of at most `max_len` columns; reserves the scratch.
 sw_status align_block(sw_bank* b, SwkAlign& p, size_t nh, uint32_t max_len) {
   const uint32_t scols = std::max(max_len, 1u);
   const size_t budget = (size_t)std::max(1, env_int("SWBANK_EDGE_MB", 2048)) << 20;
   const size_t waves = swk_i32_waves(nh, scols, budget);
+  const size_t nq = query_count(b);
   HIPOK(b, b->al_scr.reserve(waves * 2 * scols));
   p.gotoh = b->gotoh() ? 1 : 0;
   p.n_hits = nh;
-  p.query = b->al_tab.p;
-  p.qlen = (uint32_t)b->query.size();
-  p.mat = reinterpret_cast<const int8_t*>(b->al_tab.p + b->query.size());
+  p.qtab = reinterpret_cast<const uint2*>(b->al_tab.p);
+  p.nq = (uint32_t)nq;
+  p.mat = reinterpret_cast<const int8_t*>(b->al_tab.p + nq * sizeof(uint2));
+  p.query = b->al_tab.p + nq * sizeof(uint2) + b->matrix.size();
+  p.qlen = (uint32_t)b->query.size();  // (a set: its longest query)
   p.alpha = (uint32_t)b->alpha;
   p.pad = b->pad;
   p.padscore = (int32_t)b->S - 255;
@@ -79,26 +128,34 @@ sw_status paths_by_slot(sw_bank* b, const SwkAlign& p, uint32_t max_len, hipStre
   return SW_OK;
 }
 
-void name_kernel(sw_bank* b, size_t hits, size_t chunks) {
-  snprintf(b->last_kernel, sizeof(b->last_kernel), "align i32 hits=%zu chunks=%zu", hits, chunks);
+void name_kernel(sw_bank* b, bool set, size_t hits, size_t chunks) {
+  if (set)
+    snprintf(b->last_kernel, sizeof(b->last_kernel), "align-set i32 nq=%zu hits=%zu chunks=%zu",
+             query_count(b), hits, chunks);
+  else
+    snprintf(b->last_kernel, sizeof(b->last_kernel), "align i32 hits=%zu chunks=%zu", hits, chunks);
 }
 
-sw_status device_call(sw_bank* b, const uint8_t* d_res, const uint64_t* d_offs,
-                      const uint32_t* d_lens, const uint64_t* d_ids, uint32_t max_len,
-                      const uint64_t* d_hits, size_t n_hits, sw_alignment* d_out,
-                      uint32_t* d_cigar, uint32_t stride, hipStream_t hs) {
+sw_status device_launch(sw_bank* b, const uint8_t* d_res, const uint64_t* d_offs,
+                        const uint32_t* d_lens, const uint64_t* d_ids, size_t n, uint32_t max_len,
+                        const Pairs& pr, sw_alignment* d_out, uint32_t* d_cigar, uint32_t stride,
+                        hipStream_t hs) {
   SwkAlign p{};
   p.res = d_res;
   p.offs = d_offs;
   p.lens = d_lens;
   p.ids = d_ids;
-  p.hits = d_hits;
+  p.hits = pr.hits;
+  p.set = pr.set ? 1 : 0;
+  p.n = n;
+  p.hit_queries = pr.hit_queries;
+  p.hits_per_query = (uint32_t)pr.hits_per_query;
   p.out = d_out;
   p.cigar = d_cigar;
   p.cigar_stride = d_cigar ? stride : 0;
-  sw_status st = align_block(b, p, n_hits, max_len);
+  sw_status st = align_block(b, p, pr.n_hits, max_len);
   if (st != SW_OK) return st;
-  HIPOK(b, hipStreamWaitEvent(hs, b->ev_ready, 0));  // the query's codes are uploaded
+  HIPOK(b, hipStreamWaitEvent(hs, b->ev_ready, 0));  // the queries' codes are uploaded
   HIPOK(b, hipStreamWaitEvent(hs, b->ev_used, 0));   // bank scratch is free
   Timed ab{b, hs};
   if ((st = ab.begin()) != SW_OK) return st;
@@ -112,96 +169,106 @@ sw_status device_call(sw_bank* b, const uint8_t* d_res, const uint64_t* d_offs,
     if ((st = cd.end()) != SW_OK) return st;
   }
   HIPOK(b, hipEventRecord(b->ev_used, hs));
-  name_kernel(b, n_hits, chunks);
+  name_kernel(b, pr.set, pr.n_hits, chunks);
   return SW_OK;
 }
 
-}  // namespace
-
-extern "C" sw_status sw_align_hits_device(sw_bank* b, const uint8_t* d_res,
-                                          const uint64_t* d_offs, const uint32_t* d_lens,
-                                          const uint64_t* d_ids, size_t n, uint32_t max_len,
-                                          const uint64_t* d_hits, size_t n_hits,
-                                          sw_alignment* d_out, uint32_t* d_cigar,
-                                          uint32_t cigar_stride, void* stream) {
+// sw_align_hits_device and sw_align_set_hits_device.
+sw_status device_call(sw_bank* b, const uint8_t* d_res, const uint64_t* d_offs,
+                      const uint32_t* d_lens, const uint64_t* d_ids, size_t n, uint32_t max_len,
+                      const Pairs& pr, sw_alignment* d_out, uint32_t* d_cigar,
+                      uint32_t cigar_stride, void* stream) {
   DevGuard dev_guard(b);  // on the bank's device; the caller's is restored on return (ABI 6)
   if (!b) return SW_ERR_ARG;
   if (b->is_multi()) {  // on the root device, where the caller's buffers are
     sw_bank* k = b->kids[0];
     if (!b->have_query) return fail(b, SW_ERR_STATE, "penalties or query not loaded");
-    if (b->qset.size() > 1)
+    if (!pr.set && b->qset.size() > 1)
       return fail(b, SW_ERR_STATE, "a query set is loaded: alignments take one query");
-    const sw_status st = sw_align_hits_device(k, d_res, d_offs, d_lens, d_ids, n, max_len, d_hits,
-                                              n_hits, d_out, d_cigar, cigar_stride,
-                                              stream ? stream : k->stream);
+    const sw_status st = device_call(k, d_res, d_offs, d_lens, d_ids, n, max_len, pr, d_out,
+                                     d_cigar, cigar_stride, stream ? stream : k->stream);
     if (st != SW_OK) return fail(b, st, "device %d: %s", k->device, k->err);
     snprintf(b->last_kernel, sizeof(b->last_kernel), "%s", k->last_kernel);
     return SW_OK;
   }
   // a hand-off fault latched by an earlier device call is returned before anything runs
   if (const sw_status fs = take_fault(b, 0); fs != SW_OK) return fs;
-  sw_status st = align_ready(b);
+  sw_status st = align_ready(b, pr.set);
   if (st != SW_OK) return st;
-  if (n_hits == 0) return SW_OK;
-  if (!d_res || !d_offs || !d_lens || !d_hits || !d_out || n == 0)
+  if (pr.n_hits == 0) return SW_OK;
+  if (!d_res || !d_offs || !d_lens || (!pr.set && !pr.hits) || !d_out || n == 0)
     return fail(b, SW_ERR_ARG, "null device buffer or an empty batch");
-  if (n_hits > 0xFFFFFFFFull) return fail(b, SW_ERR_ARG, "hit lists hold < 2^32 hits");
-  if (d_cigar && cigar_stride && (uint64_t)n_hits * cigar_stride > 0xFFFFFFFFull)
+  if ((st = check_pairs(b, pr, n)) != SW_OK) return st;
+  if (d_cigar && cigar_stride && (uint64_t)pr.n_hits * cigar_stride > 0xFFFFFFFFull)
     return fail(b, SW_ERR_ARG, "n_hits x cigar_stride must fit 32 bits (cigar_offset)");
   HIPOK(b, hipSetDevice(b->device));
   hipStream_t hs = stream ? reinterpret_cast<hipStream_t>(stream) : b->stream;
-  return device_call(b, d_res, d_offs, d_lens, d_ids, max_len, d_hits, n_hits, d_out, d_cigar,
-                     cigar_stride, hs);
+  return device_launch(b, d_res, d_offs, d_lens, d_ids, n, max_len, pr, d_out, d_cigar,
+                       cigar_stride, hs);
 }
 
-extern "C" sw_status sw_align_hits(sw_bank* b, const uint8_t* residues, size_t residues_len,
-                                   const uint64_t* offsets, const uint32_t* lens,
-                                   const uint64_t* ids, size_t n, const uint64_t* hits,
-                                   size_t n_hits, sw_alignment* out, uint32_t* cigar,
-                                   size_t cigar_cap, size_t* cigar_used) {
+// sw_align_hits and sw_align_set_hits.
+sw_status host_call(sw_bank* b, const uint8_t* residues, size_t residues_len,
+                    const uint64_t* offsets, const uint32_t* lens, const uint64_t* ids, size_t n,
+                    const Pairs& pr, sw_alignment* out, uint32_t* cigar, size_t cigar_cap,
+                    size_t* cigar_used) {
   DevGuard dev_guard(b);  // on the bank's device; the caller's is restored on return (ABI 6)
   if (!b) return SW_ERR_ARG;
   if (cigar_used) *cigar_used = 0;
   if (b->is_multi()) {  // on the root device: hit lists are small
     sw_bank* k = b->kids[0];
     if (!b->have_query) return fail(b, SW_ERR_STATE, "penalties or query not loaded");
-    if (b->qset.size() > 1)
+    if (!pr.set && b->qset.size() > 1)
       return fail(b, SW_ERR_STATE, "a query set is loaded: alignments take one query");
-    const sw_status st = sw_align_hits(k, residues, residues_len, offsets, lens, ids, n, hits,
-                                       n_hits, out, cigar, cigar_cap, cigar_used);
+    const sw_status st = host_call(k, residues, residues_len, offsets, lens, ids, n, pr, out, cigar,
+                                   cigar_cap, cigar_used);
     if (st != SW_OK) return fail(b, st, "device %d: %s", k->device, k->err);
     snprintf(b->last_kernel, sizeof(b->last_kernel), "%s", k->last_kernel);
     return SW_OK;
   }
-  sw_status st = align_ready(b);
+  sw_status st = align_ready(b, pr.set);
   if (st != SW_OK) return st;
+  const size_t n_hits = pr.n_hits;
   if (n_hits == 0) return SW_OK;
-  if (!offsets || !lens || !hits || !out) return fail(b, SW_ERR_ARG, "null host buffer");
-  if (n_hits > 0xFFFFFFFFull) return fail(b, SW_ERR_ARG, "hit lists hold < 2^32 hits");
-  // validate and gather the listed targets (a repeated hit is gathered again)
+  if (!offsets || !lens || (!pr.set && !pr.hits) || !out)
+    return fail(b, SW_ERR_ARG, "null host buffer");
+  if ((st = check_pairs(b, pr, n)) != SW_OK) return st;
+  // validate and gather the listed targets (a repeated hit is gathered again); a set call also
+  // lists each hit's query (SW_QUERY_NONE for a slot that names no pair: nothing is gathered)
+  const size_t nq = query_count(b);
+  const auto target_of = [&](size_t h) { return pr.hits ? pr.hits[h] : (uint64_t)h; };
   std::vector<uint64_t> goffs(n_hits);
-  std::vector<uint32_t> glens(n_hits);
+  std::vector<uint32_t> glens(n_hits), gq(pr.set ? n_hits : 0);
   uint64_t total = 0;
   uint32_t max_len = 0;
   for (size_t h = 0; h < n_hits; ++h) {
-    const uint64_t t = hits[h];
+    const uint64_t t = target_of(h);
+    goffs[h] = total;
+    glens[h] = 0;
+    if (pr.set) {
+      const uint32_t qi = pr.hit_queries ? pr.hit_queries[h] : (uint32_t)(h / pr.hits_per_query);
+      gq[h] = qi == SW_QUERY_NONE || t == SW_HIT_NONE ? SW_QUERY_NONE : qi;
+      if (qi != SW_QUERY_NONE && qi >= nq)
+        return fail(b, SW_ERR_ARG, "hit %zu: query %u >= nq = %zu", h, qi, nq);
+      if (t == SW_HIT_NONE) continue;
+    }
     if (t >= n) return fail(b, SW_ERR_ARG, "hit %zu: target %llu >= n = %zu", h,
                             (unsigned long long)t, n);
+    if (pr.set && gq[h] == SW_QUERY_NONE) continue;
     const uint64_t o = offsets[t], l = lens[t];
     if (l && (!residues || o > residues_len || l > residues_len - o))
       return fail(b, SW_ERR_ARG, "target %llu outside the residues", (unsigned long long)t);
-    goffs[h] = total;
     glens[h] = (uint32_t)l;
     total += l;
     max_len = std::max(max_len, (uint32_t)l);
   }
   std::vector<uint8_t> gres(std::max<uint64_t>(total, 1), 0);
   for (size_t h = 0; h < n_hits; ++h) {
-    const uint8_t* src = glens[h] ? residues + offsets[hits[h]] : nullptr;
+    const uint8_t* src = glens[h] ? residues + offsets[target_of(h)] : nullptr;
     for (uint32_t i = 0; i < glens[h]; ++i) {
       if (src[i] >= (uint32_t)b->alpha)
         return fail(b, SW_ERR_ARG, "target %llu code %u at %u outside alphabet %d",
-                    (unsigned long long)hits[h], src[i], i, b->alpha);
+                    (unsigned long long)target_of(h), src[i], i, b->alpha);
       gres[goffs[h] + i] = src[i];
     }
   }
@@ -211,17 +278,26 @@ extern "C" sw_status sw_align_hits(sw_bank* b, const uint8_t* residues, size_t r
   HIPOK(b, b->al_offs.reserve(n_hits));
   HIPOK(b, b->al_lens.reserve(n_hits));
   HIPOK(b, b->al_out.reserve(n_hits));
+  if (pr.set) HIPOK(b, b->al_hq.reserve(n_hits));
   HIPOK(b, hipStreamWaitEvent(hs, b->ev_ready, 0));
   HIPOK(b, hipStreamWaitEvent(hs, b->ev_used, 0));  // an earlier call may still read the buffers
   HIPOK(b, hipMemcpyAsync(b->al_res.p, gres.data(), gres.size(), hipMemcpyHostToDevice, hs));
   HIPOK(b, hipMemcpyAsync(b->al_offs.p, goffs.data(), n_hits * 8, hipMemcpyHostToDevice, hs));
   HIPOK(b, hipMemcpyAsync(b->al_lens.p, glens.data(), n_hits * 4, hipMemcpyHostToDevice, hs));
-  __atomic_fetch_add(&b->ctr.h2d_bytes, gres.size() + n_hits * 12, __ATOMIC_RELAXED);
+  if (pr.set)
+    HIPOK(b, hipMemcpyAsync(b->al_hq.p, gq.data(), n_hits * 4, hipMemcpyHostToDevice, hs));
+  __atomic_fetch_add(&b->ctr.h2d_bytes, gres.size() + n_hits * (pr.set ? 16 : 12),
+                     __ATOMIC_RELAXED);
   SwkAlign p{};
   p.res = b->al_res.p;
   p.offs = b->al_offs.p;
   p.lens = b->al_lens.p;
   p.out = b->al_out.p;
+  if (pr.set) {  // the gathered batch: hit h is target h against query al_hq[h]
+    p.set = 1;
+    p.n = n_hits;
+    p.hit_queries = b->al_hq.p;
+  }
   if ((st = align_block(b, p, n_hits, max_len)) != SW_OK) return st;
   Timed ab{b, hs};
   if ((st = ab.begin()) != SW_OK) return st;
@@ -306,10 +382,58 @@ extern "C" sw_status sw_align_hits(sw_bank* b, const uint8_t* residues, size_t r
   }
   HIPOK(b, hipEventRecord(b->ev_used, hs));
   for (size_t h = 0; h < n_hits; ++h) {  // the records speak of the caller's batch
-    out[h].index = hits[h];
-    out[h].id = ids ? ids[hits[h]] : hits[h];
     if (!(cigar && cigar_cap)) out[h].cigar_offset = 0;
+    if (out[h].flags & SW_ALIGN_NO_HIT) continue;  // (index = id = SW_HIT_NONE)
+    const uint64_t t = target_of(h);
+    out[h].index = t;
+    out[h].id = ids ? ids[t] : t;
   }
-  name_kernel(b, n_hits, chunks);
+  name_kernel(b, pr.set, n_hits, chunks);
   return SW_OK;
+}
+
+}  // namespace
+
+extern "C" sw_status sw_align_hits_device(sw_bank* b, const uint8_t* d_res,
+                                          const uint64_t* d_offs, const uint32_t* d_lens,
+                                          const uint64_t* d_ids, size_t n, uint32_t max_len,
+                                          const uint64_t* d_hits, size_t n_hits,
+                                          sw_alignment* d_out, uint32_t* d_cigar,
+                                          uint32_t cigar_stride, void* stream) {
+  return device_call(b, d_res, d_offs, d_lens, d_ids, n, max_len,
+                     Pairs{false, nullptr, 0, d_hits, n_hits}, d_out, d_cigar, cigar_stride,
+                     stream);
+}
+
+extern "C" sw_status sw_align_hits(sw_bank* b, const uint8_t* residues, size_t residues_len,
+                                   const uint64_t* offsets, const uint32_t* lens,
+                                   const uint64_t* ids, size_t n, const uint64_t* hits,
+                                   size_t n_hits, sw_alignment* out, uint32_t* cigar,
+                                   size_t cigar_cap, size_t* cigar_used) {
+  return host_call(b, residues, residues_len, offsets, lens, ids, n,
+                   Pairs{false, nullptr, 0, hits, n_hits}, out, cigar, cigar_cap, cigar_used);
+}
+
+extern "C" sw_status sw_align_set_hits_device(sw_bank* b, const uint8_t* d_res,
+                                              const uint64_t* d_offs, const uint32_t* d_lens,
+                                              const uint64_t* d_ids, size_t n, uint32_t max_len,
+                                              const uint32_t* d_hit_queries,
+                                              size_t hits_per_query, const uint64_t* d_hits,
+                                              size_t n_hits, sw_alignment* d_out,
+                                              uint32_t* d_cigar, uint32_t cigar_stride,
+                                              void* stream) {
+  return device_call(b, d_res, d_offs, d_lens, d_ids, n, max_len,
+                     Pairs{true, d_hit_queries, hits_per_query, d_hits, n_hits}, d_out, d_cigar,
+                     cigar_stride, stream);
+}
+
+extern "C" sw_status sw_align_set_hits(sw_bank* b, const uint8_t* residues, size_t residues_len,
+                                       const uint64_t* offsets, const uint32_t* lens,
+                                       const uint64_t* ids, size_t n,
+                                       const uint32_t* hit_queries, size_t hits_per_query,
+                                       const uint64_t* hits, size_t n_hits, sw_alignment* out,
+                                       uint32_t* cigar, size_t cigar_cap, size_t* cigar_used) {
+  return host_call(b, residues, residues_len, offsets, lens, ids, n,
+                   Pairs{true, hit_queries, hits_per_query, hits, n_hits}, out, cigar, cigar_cap,
+                   cigar_used);
 }

@@ -4,7 +4,8 @@
 // (kernel choice and launches, the device-buffer API), swbank_feeder.hip (the chunked
 // host-buffer feeder and the host API), swbank_stream.hip (streamed host batches, one kernel
 // per call), swbank_multi.hip (multi-device banks and the RCCL gather), swbank_align.hip
-// (alignments of chosen hits), swbank_top.hip (the k best hits of a score matrix).
+// (alignments of chosen hits, of one query or a query set), swbank_top.hip (the k best hits of
+// every row of a score matrix, the best query of every column).
 #ifndef SWBANK_BANK_H
 #define SWBANK_BANK_H
 
@@ -105,6 +106,11 @@ extern "C" hipError_t swk_top_hits(const int32_t* scores, const uint64_t* ids, s
                                    size_t k, int32_t min_score, unsigned long long* state,
                                    unsigned long long* keys, uint64_t* hits, int32_t* hit_scores,
                                    uint64_t* hit_ids, uint32_t* counts, hipStream_t st);
+// swbank_kbestq.hip: keys of swk_best_queries' split form (0 when the call needs none)
+extern "C" size_t swk_best_queries_keys(size_t n, size_t nq);
+extern "C" hipError_t swk_best_queries(const int32_t* scores, size_t n, size_t nq,
+                                       int32_t min_score, unsigned long long* keys,
+                                       uint32_t* best_query, int32_t* best_score, hipStream_t st);
 
 // ---- helpers shared by the units ----------------------------------------------------
 inline int env_int(const char* name, int dflt) {
@@ -420,20 +426,23 @@ struct sw_bank {
   uint32_t i32_strips = 0;
   DevBuf<uint2> i32prof, i32scr;
   DevBuf<unsigned long long> best_key;  // sw_best_hit_device scratch
-  // alignments of chosen hits (swbank_align.hip): the query's codes and the matrix on the
-  // device (al_tab: codes, then alpha x alpha scores; built on first use per query), per-wave
+  // alignments of chosen hits (swbank_align.hip): the queries' codes and the matrix on the
+  // device (al_tab: an {offset, length} entry per query, alpha x alpha scores, then the codes of
+  // the query or of every query of the set; built on first use per query or set), per-wave
   // scratch rows, the direction store; the host-buffer call's gathered targets, records, ops,
-  // window plan and chunk lists
+  // window plan and chunk lists, and (a set call) each hit's query
   bool al_ready = false;
   DevBuf<uint8_t> al_tab, al_res;
   DevBuf<uint2> al_scr;
-  DevBuf<uint32_t> al_dirs, al_lens, al_cig, al_list;
+  DevBuf<uint32_t> al_dirs, al_lens, al_cig, al_list, al_hq;
   DevBuf<uint64_t> al_offs;
   DevBuf<sw_alignment> al_out;
   DevBuf<SwkAlignPlan> al_plan;
   // the k best hits (swbank_top.hip): the select's per-row state and key slots; the host call's
   // scores and results on the device; ev_top follows the last call's use of the four, on
-  // whichever stream it ran, and the next call's stream waits for it
+  // whichever stream it ran, and the next call's stream waits for it.  The column best
+  // (sw_best_queries*) borrows them under the same event: top_keys for a split query axis,
+  // top_scores / top_cnt / top_hsc for the host call's matrix, best queries and best scores
   DevBuf<unsigned long long> top_state, top_keys;
   DevBuf<int32_t> top_scores, top_hsc;
   DevBuf<uint64_t> top_hits;

@@ -209,6 +209,7 @@ extern "C" void sw_bank_destroy(sw_bank* b) {
   b->al_lens.release();
   b->al_cig.release();
   b->al_list.release();
+  b->al_hq.release();
   b->al_offs.release();
   b->al_out.release();
   b->al_plan.release();
@@ -504,6 +505,7 @@ extern "C" sw_status sw_load_queries(sw_bank* b, size_t nq, const uint64_t* ids,
   b->have_query = true;
   b->dirty = true;
   b->mq_ready = false;
+  b->al_ready = false;  // (the alignment calls' copy of the set)
   return SW_OK;
 }
 

@@ -17,6 +17,10 @@
 //           T = max(f, M - o - e, I - e)
 // (merged: the HDL's first-column rule is not applied; the host refuses the one case in which
 // it changes a score, max(s) > o + e.)
+//
+// The kernels are templated on SET: the SET instances serve sw_align_set_hits* and take each
+// hit's query from a table of the loaded set (al_query); the others are the single-query
+// kernels, which the set costs nothing.
 #include "swbank.h"
 #include "swbank_align.h"
 #include "swbank_kcommon.h"
@@ -55,7 +59,35 @@ struct AlignArgs {
   const SwkAlignPlan* plan;  // optional, per position; else slot k of `slot` dwords
   uint64_t slot;
   uint32_t* dirs;
+  // a query set (the SET kernels): query i's codes at query + qtab[i].x, qtab[i].y of them; hit
+  // h's query is hit_queries[h], or h / hits_per_query; n targets in the batch
+  const uint2* qtab;
+  const uint32_t* hit_queries;
+  uint32_t nq, hits_per_query;
+  size_t n;
 };
+
+// Hit h's query.  !SET: the one loaded query.  SET: the hit's own; len = 0xFFFFFFFF when the hit
+// names no query (SW_QUERY_NONE, or any index past the set: nothing is read for it).
+struct AlQuery {
+  const uint8_t* p;
+  uint32_t len;
+};
+constexpr uint32_t AL_NO_QUERY = 0xFFFFFFFFu;
+// UNIFORM: h is the same in every lane of the wave (passes A-C); the entry goes to SGPRs.
+template <bool SET, bool UNIFORM>
+__device__ __forceinline__ AlQuery al_query(const AlignArgs& a, size_t h) {
+  if constexpr (!SET) return AlQuery{a.query, a.qlen};
+  uint32_t qi = a.hit_queries ? a.hit_queries[h] : (uint32_t)h / a.hits_per_query;
+  if constexpr (UNIFORM) qi = __builtin_amdgcn_readfirstlane(qi);
+  if (qi >= a.nq) return AlQuery{a.query, AL_NO_QUERY};
+  uint2 e = a.qtab[qi];
+  if constexpr (UNIFORM) {
+    e.x = __builtin_amdgcn_readfirstlane(e.x);
+    e.y = __builtin_amdgcn_readfirstlane(e.y);
+  }
+  return AlQuery{a.query + e.x, e.y};
+}
 
 __device__ __forceinline__ int32_t al_lane0(int32_t inj, int32_t v) {  // wave_shr:1
   return __builtin_amdgcn_update_dpp(inj, v, 0x138, 0xF, 0xF, false);
@@ -220,7 +252,9 @@ __device__ __forceinline__ void al_load_matrix(const AlignArgs& a, int8_t* smat)
 
 // Passes A and B: score and end cell (forward), start cell (the same walk over the reversed
 // prefixes q[q_end..0] x t[t_end..0]); writes the hit's whole record, without a path.
-template <bool GOTOH>
+// SET: the hit's own query of a set; a hit that names no pair gets its record here (index = id =
+// SW_HIT_NONE, SW_ALIGN_EMPTY | SW_ALIGN_NO_HIT) and nothing of the batch is read for it.
+template <bool GOTOH, bool SET>
 __global__ void __launch_bounds__(256) align_ends(const AlignArgs a) {
   __shared__ uint2 lp[4][AL_LETTERS][64];
   __shared__ int8_t smat[AL_LETTERS * AL_LETTERS];
@@ -231,12 +265,29 @@ __global__ void __launch_bounds__(256) align_ends(const AlignArgs a) {
   uint2* const scr[2] = {a.scratch + gw * 2 * a.scols, a.scratch + gw * 2 * a.scols + a.scols};
   for (size_t h = gw; h < a.n_hits; h += GW) {
     const uint64_t t = a.hits ? a.hits[h] : (uint64_t)h;
+    const AlQuery qy = al_query<SET, true>(a, h);
+    if constexpr (SET) {
+      if (qy.len == AL_NO_QUERY || t >= a.n) {
+        if (lane == 0) {
+          sw_alignment r;
+          r.index = r.id = SW_HIT_NONE;
+          r.score = 0;
+          r.flags = (uint32_t)SW_ALIGN_EMPTY | (uint32_t)SW_ALIGN_NO_HIT;
+          r.q_start = r.q_end = r.t_start = r.t_end = 0u;
+          r.n_columns = r.n_identities = 0;
+          r.cigar_offset = a.cigar_stride ? (uint32_t)(h * a.cigar_stride) : 0u;
+          r.cigar_len = 0;
+          a.out[h] = r;
+        }
+        continue;
+      }
+    }
     uint32_t L = a.lens[t];
     const uint8_t* tp = a.res + (L ? a.offs[t] : 0);
     L = __builtin_amdgcn_readfirstlane(min(L, a.scols));
     int32_t score, rs;
     uint32_t qe, te, ri, rj;
-    al_walk<GOTOH, false>(a, smat, lp[wave], scr, AlSeq{a.query, tp, 1, 1, a.qlen, L}, nullptr,
+    al_walk<GOTOH, false>(a, smat, lp[wave], scr, AlSeq{qy.p, tp, 1, 1, qy.len, L}, nullptr,
                           score, qe, te);
     score = __builtin_amdgcn_readfirstlane(score);
     qe = __builtin_amdgcn_readfirstlane(qe);
@@ -244,7 +295,7 @@ __global__ void __launch_bounds__(256) align_ends(const AlignArgs a) {
     uint32_t qs = 0, ts = 0;
     if (score > 0) {
       al_walk<GOTOH, false>(a, smat, lp[wave], scr,
-                            AlSeq{a.query + qe, tp + te, -1, -1, qe + 1, te + 1}, nullptr, rs, ri,
+                            AlSeq{qy.p + qe, tp + te, -1, -1, qe + 1, te + 1}, nullptr, rs, ri,
                             rj);
       qs = qe - min(ri, qe);
       ts = te - min(rj, te);
@@ -269,13 +320,15 @@ __global__ void __launch_bounds__(256) align_ends(const AlignArgs a) {
 
 struct AlWindow {
   size_t h;
+  const uint8_t* qp;  // the hit's query (valid when ok)
   uint32_t qs, ts, Q, L;
   uint64_t dir_off, cig_off;
   uint32_t cig_cap;
   bool ok;
 };
 // Position k's hit, window and places in the direction store and the CIGAR buffer; !ok when the
-// hit has no path to store (score 0, or a window past its slot).
+// hit has no path to store (score 0, a slot that names no pair, or a window past its slot).
+template <bool SET, bool UNIFORM>
 __device__ __forceinline__ AlWindow al_window(const AlignArgs& a, size_t k) {
   AlWindow w;
   w.h = a.list ? (size_t)a.list[k] : a.h0 + k;
@@ -296,13 +349,19 @@ __device__ __forceinline__ AlWindow al_window(const AlignArgs& a, size_t k) {
     w.cig_off = (uint64_t)w.h * a.cigar_stride;
     w.cig_cap = a.cigar_stride;
   }
-  w.ok = r.score > 0 && r.q_end >= r.q_start && r.t_end >= r.t_start && r.q_end < a.qlen &&
-         w.L <= a.scols && al_dir_dwords(w.Q, w.L) <= cap;
+  w.qp = a.query;
+  w.ok = r.score > 0 && r.q_end >= r.q_start && r.t_end >= r.t_start && w.L <= a.scols &&
+         al_dir_dwords(w.Q, w.L) <= cap;
+  if (w.ok) {  // (the record of a slot without a pair scores 0: its query is never looked up)
+    const AlQuery qy = al_query<SET, UNIFORM>(a, w.h);
+    w.qp = qy.p;
+    w.ok = qy.len != AL_NO_QUERY && r.q_end < qy.len;
+  }
   return w;
 }
 
 // Pass C: the direction store of each window.
-template <bool GOTOH>
+template <bool GOTOH, bool SET>
 __global__ void __launch_bounds__(256) align_dirs(const AlignArgs a) {
   __shared__ uint2 lp[4][AL_LETTERS][64];
   __shared__ int8_t smat[AL_LETTERS * AL_LETTERS];
@@ -311,13 +370,13 @@ __global__ void __launch_bounds__(256) align_dirs(const AlignArgs a) {
   const size_t gw = (size_t)blockIdx.x * 4 + wave, GW = (size_t)gridDim.x * 4;
   uint2* const scr[2] = {a.scratch + gw * 2 * a.scols, a.scratch + gw * 2 * a.scols + a.scols};
   for (size_t k = gw; k < a.count; k += GW) {
-    const AlWindow w = al_window(a, k);
+    const AlWindow w = al_window<SET, true>(a, k);
     if (!w.ok) continue;
     const uint8_t* tp = a.res + a.offs[a.out[w.h].index] + w.ts;
     int32_t b0;
     uint32_t b1, b2;
     al_walk<GOTOH, true>(a, smat, lp[wave], scr,
-                         AlSeq{a.query + w.qs, tp, 1, 1,
+                         AlSeq{w.qp + w.qs, tp, 1, 1,
                                (uint32_t)__builtin_amdgcn_readfirstlane(w.Q),
                                (uint32_t)__builtin_amdgcn_readfirstlane(w.L)},
                          a.dirs + w.dir_off, b0, b1, b2);
@@ -326,15 +385,15 @@ __global__ void __launch_bounds__(256) align_dirs(const AlignArgs a) {
 
 // Pass D: one lane per hit follows the bits from the end cell to the start cell, counts columns
 // and identities, emits run-length ops backwards and reverses them in place.
-template <bool GOTOH>
+template <bool GOTOH, bool SET>
 __global__ void __launch_bounds__(64) align_path(const AlignArgs a) {
   const size_t k = (size_t)blockIdx.x * 64 + threadIdx.x;
   if (k >= a.count) return;
-  const AlWindow w = al_window(a, k);
+  const AlWindow w = al_window<SET, false>(a, k);
   if (!w.ok || w.cig_cap == 0) return;
   sw_alignment& r = a.out[w.h];
   const uint8_t* tp = a.res + a.offs[r.index] + w.ts;
-  const uint8_t* qp = a.query + w.qs;
+  const uint8_t* qp = w.qp + w.qs;
   const uint8_t* db = reinterpret_cast<const uint8_t*>(a.dirs + w.dir_off);
   uint32_t* cig = a.cigar + w.cig_off;
   const uint64_t nsteps = (uint64_t)w.L + 63;
@@ -440,12 +499,19 @@ static swk::AlignArgs align_args(const SwkAlign* p) {
   a.cigar_stride = p->cigar_stride;
   a.scratch = static_cast<uint2*>(p->scratch);
   a.scols = p->scols;
+  a.qtab = p->qtab;
+  a.hit_queries = p->hit_queries;
+  a.nq = p->nq;
+  a.hits_per_query = p->hits_per_query;
+  a.n = p->n;
   return a;
 }
 
 static bool align_args_ok(const SwkAlign* p) {
   return p && p->alpha >= 1 && p->alpha < (uint32_t)swk::AL_LETTERS &&
-         p->pad < (uint32_t)swk::AL_LETTERS && p->waves && p->waves % 4 == 0 && p->scols;
+         p->pad < (uint32_t)swk::AL_LETTERS && p->waves && p->waves % 4 == 0 && p->scols &&
+         (!p->set || (p->qtab && p->nq && (p->hit_queries != nullptr) != (p->hits_per_query != 0) &&
+                      p->n_hits <= 0xFFFFFFFFull));
 }
 
 // Passes A and B for hits [0, n_hits): every record written, paths left out.
@@ -454,10 +520,15 @@ extern "C" hipError_t swk_launch_align_ends(const SwkAlign* p, hipStream_t st) {
   if (!align_args_ok(p)) return hipErrorInvalidValue;
   const swk::AlignArgs a = align_args(p);
   const dim3 grid((unsigned)(p->waves / 4));
-  if (p->gotoh)
-    hipLaunchKernelGGL(swk::align_ends<true>, grid, dim3(256), 0, st, a);
+  // (the single-query kernels are their own instantiation: the set's lookups cost them nothing)
+  if (p->gotoh && p->set)
+    hipLaunchKernelGGL((swk::align_ends<true, true>), grid, dim3(256), 0, st, a);
+  else if (p->gotoh)
+    hipLaunchKernelGGL((swk::align_ends<true, false>), grid, dim3(256), 0, st, a);
+  else if (p->set)
+    hipLaunchKernelGGL((swk::align_ends<false, true>), grid, dim3(256), 0, st, a);
   else
-    hipLaunchKernelGGL(swk::align_ends<false>, grid, dim3(256), 0, st, a);
+    hipLaunchKernelGGL((swk::align_ends<false, false>), grid, dim3(256), 0, st, a);
   return hipGetLastError();
 }
 
@@ -477,12 +548,18 @@ extern "C" hipError_t swk_launch_align_paths(const SwkAlign* p, const uint32_t* 
   a.dirs = dirs;
   const dim3 grid((unsigned)(std::min<size_t>(p->waves, (count + 3) / 4 * 4) / 4));
   const dim3 pgrid((unsigned)((count + 63) / 64));
-  if (p->gotoh) {
-    hipLaunchKernelGGL(swk::align_dirs<true>, grid, dim3(256), 0, st, a);
-    hipLaunchKernelGGL(swk::align_path<true>, pgrid, dim3(64), 0, st, a);
+  if (p->gotoh && p->set) {
+    hipLaunchKernelGGL((swk::align_dirs<true, true>), grid, dim3(256), 0, st, a);
+    hipLaunchKernelGGL((swk::align_path<true, true>), pgrid, dim3(64), 0, st, a);
+  } else if (p->gotoh) {
+    hipLaunchKernelGGL((swk::align_dirs<true, false>), grid, dim3(256), 0, st, a);
+    hipLaunchKernelGGL((swk::align_path<true, false>), pgrid, dim3(64), 0, st, a);
+  } else if (p->set) {
+    hipLaunchKernelGGL((swk::align_dirs<false, true>), grid, dim3(256), 0, st, a);
+    hipLaunchKernelGGL((swk::align_path<false, true>), pgrid, dim3(64), 0, st, a);
   } else {
-    hipLaunchKernelGGL(swk::align_dirs<false>, grid, dim3(256), 0, st, a);
-    hipLaunchKernelGGL(swk::align_path<false>, pgrid, dim3(64), 0, st, a);
+    hipLaunchKernelGGL((swk::align_dirs<false, false>), grid, dim3(256), 0, st, a);
+    hipLaunchKernelGGL((swk::align_path<false, false>), pgrid, dim3(64), 0, st, a);
   }
   return hipGetLastError();
 }

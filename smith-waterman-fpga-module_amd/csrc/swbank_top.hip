@@ -1,5 +1,6 @@
 // swbank_top.hip — the k best hits of every row of a score matrix (include/swbank.h "the k best
-// hits"): the two ABI entries.  The kernels are in swbank_ktop.hip.
+// hits") and the best query of every column ("the best query per target",
+// §3.11): the ABI entries.  The kernels are in swbank_ktop.hip and swbank_kbestq.hip.
 #include "swbank_bank.h"
 
 namespace {
@@ -47,7 +48,109 @@ sw_status select_on(sw_bank* b, const int32_t* d_scores, const uint64_t* d_ids, 
   return SW_OK;
 }
 
+// ---- the best query of every column ---------------------------------------------------------
+const char* bad_best_args(const void* scores, const void* bq, const void* bs, size_t n, size_t nq) {
+  if (!scores || (!bq && !bs)) return "null scores, or neither output given";
+  if (n == 0 || nq == 0) return "n and nq must be positive";
+  if (nq > 65536) return "nq > 65536 (the limit of sw_load_queries)";
+  if (n > 0x100000000ull) return "a row holds <= 2^32 scores";
+  if (n > SIZE_MAX / sizeof(int32_t) / nq) return "nq x n overflows size_t";
+  return nullptr;
+}
+
+// The column best on `hs`, ordered after the previous use of the scratch it shares with the
+// top-hits calls (ev_top).
+sw_status best_queries_on(sw_bank* b, const int32_t* d_scores, size_t n, size_t nq,
+                          int32_t min_score, uint32_t* d_best_query, int32_t* d_best_score,
+                          hipStream_t hs) {
+  const size_t nkeys = swk_best_queries_keys(n, nq);
+  if (nkeys) HIPOK(b, b->top_keys.reserve(nkeys));
+  if (!b->ev_top) HIPOK(b, hipEventCreateWithFlags(&b->ev_top, hipEventDisableTiming));
+  else HIPOK(b, hipStreamWaitEvent(hs, b->ev_top, 0));
+  Timed t{b, hs};
+  sw_status st = t.begin();
+  if (st != SW_OK) {
+    t.drop();
+    return st;
+  }
+  const hipError_t e = swk_best_queries(d_scores, n, nq, min_score, nkeys ? b->top_keys.p : nullptr,
+                                        d_best_query, d_best_score, hs);
+  const hipError_t er = hipEventRecord(b->ev_top, hs);
+  if (e != hipSuccess || er != hipSuccess) {
+    t.drop();
+    HIPOK(b, e);
+    HIPOK(b, er);
+  }
+  if ((st = t.end()) != SW_OK) {
+    t.drop();
+    return st;
+  }
+  snprintf(b->last_kernel, sizeof(b->last_kernel), "best-query nq=%zu n=%zu", nq, n);
+  return SW_OK;
+}
+
 }  // namespace
+
+extern "C" sw_status sw_best_queries_device(sw_bank* b, const int32_t* d_scores, size_t n,
+                                            size_t nq, int32_t min_score, uint32_t* d_best_query,
+                                            int32_t* d_best_score, void* stream) {
+  DevGuard dev_guard(b);  // on the bank's device; the caller's is restored on return (ABI 6)
+  if (!b) return SW_ERR_ARG;
+  if (const char* why = bad_best_args(d_scores, d_best_query, d_best_score, n, nq))
+    return fail(b, SW_ERR_ARG, "sw_best_queries_device: %s", why);
+  if (b->is_multi()) {  // on the root device, where the multi-device calls leave the scores
+    sw_bank* r = b->kids[0];
+    const sw_status st = sw_best_queries_device(r, d_scores, n, nq, min_score, d_best_query,
+                                                d_best_score, stream ? stream : r->stream);
+    if (st != SW_OK) return fail(b, st, "device %d: %s", r->device, r->err);
+    snprintf(b->last_kernel, sizeof(b->last_kernel), "%s", r->last_kernel);
+    return SW_OK;
+  }
+  // a hand-off fault latched by an earlier device call is returned before anything runs
+  if (const sw_status fs = take_fault(b, 0); fs != SW_OK) return fs;
+  HIPOK(b, hipSetDevice(b->device));
+  return best_queries_on(b, d_scores, n, nq, min_score, d_best_query, d_best_score,
+                         stream ? reinterpret_cast<hipStream_t>(stream) : b->stream);
+}
+
+extern "C" sw_status sw_best_queries(sw_bank* b, const int32_t* scores, size_t n, size_t nq,
+                                     int32_t min_score, uint32_t* best_query,
+                                     int32_t* best_score) {
+  DevGuard dev_guard(b);  // on the bank's device; the caller's is restored on return (ABI 6)
+  if (!b) return SW_ERR_ARG;
+  if (const char* why = bad_best_args(scores, best_query, best_score, n, nq))
+    return fail(b, SW_ERR_ARG, "sw_best_queries: %s", why);
+  if (b->is_multi()) {  // on the root device
+    sw_bank* r = b->kids[0];
+    const sw_status st = sw_best_queries(r, scores, n, nq, min_score, best_query, best_score);
+    if (st != SW_OK) return fail(b, st, "device %d: %s", r->device, r->err);
+    snprintf(b->last_kernel, sizeof(b->last_kernel), "%s", r->last_kernel);
+    return SW_OK;
+  }
+  if (const sw_status fs = take_fault(b, 0); fs != SW_OK) return fs;
+  HIPOK(b, hipSetDevice(b->device));
+  hipStream_t hs = b->stream;
+  // the previous call (on any stream) is done with the buffers before they are refilled
+  if (b->ev_top) HIPOK(b, hipStreamWaitEvent(hs, b->ev_top, 0));
+  HIPOK(b, b->top_scores.reserve(nq * n));
+  if (best_query) HIPOK(b, b->top_cnt.reserve(n));
+  if (best_score) HIPOK(b, b->top_hsc.reserve(n));
+  HIPOK(b, hipMemcpyAsync(b->top_scores.p, scores, nq * n * sizeof(int32_t),
+                          hipMemcpyHostToDevice, hs));
+  const sw_status st = best_queries_on(b, b->top_scores.p, n, nq, min_score,
+                                       best_query ? b->top_cnt.p : nullptr,
+                                       best_score ? b->top_hsc.p : nullptr, hs);
+  if (st != SW_OK) return st;
+  if (best_query)
+    HIPOK(b, hipMemcpyAsync(best_query, b->top_cnt.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                            hs));
+  if (best_score)
+    HIPOK(b, hipMemcpyAsync(best_score, b->top_hsc.p, n * sizeof(int32_t), hipMemcpyDeviceToHost,
+                            hs));
+  HIPOK(b, hipEventRecord(b->ev_top, hs));  // (the copies read the result buffers)
+  HIPOK(b, hipStreamSynchronize(hs));
+  return SW_OK;
+}
 
 extern "C" sw_status sw_top_hits_device(sw_bank* b, const int32_t* d_scores, const uint64_t* d_ids,
                                         size_t n, size_t nq, size_t k, int32_t min_score,

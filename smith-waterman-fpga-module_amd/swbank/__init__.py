@@ -47,6 +47,8 @@ EXPORTS = (
     "sw_bank_counters_ex", "sw_bank_sync", "sw_score_batch_device_multi",
     "sw_align_hits", "sw_align_hits_device", "sw_cigar_string",
     "sw_top_hits", "sw_top_hits_device",
+    "sw_best_queries", "sw_best_queries_device",
+    "sw_align_set_hits", "sw_align_set_hits_device",
 )
 ABI_VERSION = 6
 COUNTERS = ("stream_calls", "stream_reruns", "stream_declined", "chunked_calls", "device_sorts",
@@ -56,9 +58,11 @@ COUNTERS = ("stream_calls", "stream_reruns", "stream_declined", "chunked_calls",
 MAX_DEVICES = 16
 CIGAR_M, CIGAR_I, CIGAR_D = 0, 1, 2          # BAM codes: I consumes query only, D target only
 ALIGN_EMPTY, ALIGN_NO_PATH = 1, 2            # sw_alignment.flags
+ALIGN_NO_HIT = 4                             # ... the slot named no pair (with ALIGN_EMPTY)
 RECORD_BYTES, RECORD_MAX_BASES = 64, 232
 TOP_MAX_K = 4096                             # SW_TOP_MAX_K: the largest k of the top-hits calls
 HIT_NONE = 0xFFFFFFFFFFFFFFFF                # SW_HIT_NONE: a hit slot past the row's count
+QUERY_NONE = 0xFFFFFFFF                      # SW_QUERY_NONE: "no query" in a hit-query list
 INT32_MIN = -(1 << 31)                       # min_score: no threshold; the score of such a slot
 
 
@@ -210,6 +214,10 @@ def lib() -> ctypes.CDLL:
         "sw_cigar_string": (sz, [P, sz, P, sz]),
         "sw_top_hits": (i32, [P, P, P, sz, sz, sz, i32, P, P, P, P]),
         "sw_top_hits_device": (i32, [P, P, P, sz, sz, sz, i32, P, P, P, P, P]),
+        "sw_best_queries": (i32, [P, P, sz, sz, i32, P, P]),
+        "sw_best_queries_device": (i32, [P, P, sz, sz, i32, P, P, P]),
+        "sw_align_set_hits": (i32, [P, P, sz, P, P, P, sz, P, sz, P, sz, P, P, sz, P]),
+        "sw_align_set_hits_device": (i32, [P, P, P, P, P, sz, u32, P, sz, P, sz, P, P, u32, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -512,6 +520,82 @@ class ScoreBank:
                                                d_lens or None, d_ids or None, n, max_len,
                                                d_hits or None, n_hits, d_out or None,
                                                d_cigar or None, cigar_stride, stream or None))
+
+    # alignments of chosen hits against a query set
+    def align_set_hits(self, residues: np.ndarray, offsets: np.ndarray, lens: np.ndarray,
+                       hits=None, hit_queries=None, hits_per_query: int = 0,
+                       ids: Optional[np.ndarray] = None, cigar_cap: Optional[int] = None,
+                       n_hits: Optional[int] = None) -> list:
+        """sw_align_set_hits: Alignment objects for the pairs of the loaded query set.  Hit h is
+        query hit_queries[h] (or h // hits_per_query, the [nq, k] layout of top_hits) against
+        target hits[h] (or target h when hits is None; n_hits then defaults to the number of
+        hit_queries, or of targets).  A hit whose query is QUERY_NONE or whose target is HIT_NONE
+        names no pair: index = id = HIT_NONE, flags ALIGN_EMPTY | ALIGN_NO_HIT.  cigar_cap as
+        for align_hits."""
+        res, offs, ln, idv = validate_batch(residues, offsets, lens, ids)
+        hv = None if hits is None else np.ascontiguousarray(hits, dtype=np.uint64).reshape(-1)
+        hq = None if hit_queries is None else \
+            np.ascontiguousarray(hit_queries, dtype=np.uint32).reshape(-1)
+        if n_hits is None:
+            n_hits = len(hv) if hv is not None else len(hq) if hq is not None else len(ln)
+        if (hv is not None and len(hv) < n_hits) or (hq is not None and len(hq) < n_hits):
+            raise ValueError("hits / hit_queries shorter than n_hits")
+        out = np.zeros(max(n_hits, 1), dtype=ALIGNMENT_DTYPE)
+        if cigar_cap is None:  # runs alternate with M runs: at most 2 x columns + 1 ops a path
+            tv = hv[:n_hits] if hv is not None else np.arange(min(n_hits, len(ln)), dtype=np.uint64)
+            sel = tv[tv < len(ln)].astype(np.int64)
+            cigar_cap = 2 * int(ln[sel].astype(np.int64).sum()) + n_hits
+        cig = np.zeros(max(cigar_cap, 1), dtype=np.uint32)
+        used = ctypes.c_size_t()
+        self._check(lib().sw_align_set_hits(
+            self._h, _p(res), res.size, _p(offs), _p(ln), _p(idv) if idv is not None else None,
+            len(ln), _p(hq) if hq is not None else None, hits_per_query,
+            _p(hv) if hv is not None else None, n_hits, _p(out), _p(cig) if cigar_cap else None,
+            cigar_cap, ctypes.byref(used)))
+        return alignments_from(out[:n_hits], cig)
+
+    def align_set_hits_device(self, d_res: int, d_offs: int, d_lens: int, n: int, max_len: int,
+                              n_hits: int, d_out: int, d_hits: int = 0, d_hit_queries: int = 0,
+                              hits_per_query: int = 0, d_cigar: int = 0, cigar_stride: int = 0,
+                              stream: int = 0, d_ids: int = 0):
+        """sw_align_set_hits_device: device pointers (ints).  Hit h's query is d_hit_queries[h]
+        (uint32) or h // hits_per_query, its target d_hits[h] (uint64) or h when d_hits is 0;
+        d_out, d_cigar and cigar_stride as for align_hits_device.  Async on `stream` (0: the
+        bank's own stream; sync() before reading)."""
+        self._check(lib().sw_align_set_hits_device(
+            self._h, d_res or None, d_offs or None, d_lens or None, d_ids or None, n, max_len,
+            d_hit_queries or None, hits_per_query, d_hits or None, n_hits, d_out or None,
+            d_cigar or None, cigar_stride, stream or None))
+
+    # the best query of every target
+    def best_queries(self, scores: np.ndarray, min_score: Optional[int] = None,
+                     want_query: bool = True, want_score: bool = True):
+        """sw_best_queries: for every column of `scores` [nq, n] the lowest query with the
+        column's maximum and that maximum, (best_query uint32 [n], best_score int32 [n]);
+        QUERY_NONE / INT32_MIN where the maximum is < min_score (None: no threshold).  An output
+        not wanted is None."""
+        s = np.ascontiguousarray(scores, dtype=np.int32)
+        if s.ndim != 2:
+            raise ValueError("scores: 2-D [nq, n]")
+        nq, n = s.shape
+        bq = np.empty(max(n, 1), np.uint32) if want_query else None
+        bs = np.empty(max(n, 1), np.int32) if want_score else None
+        self._check(lib().sw_best_queries(self._h, _p(s), n, nq,
+                                          INT32_MIN if min_score is None else min_score,
+                                          _p(bq) if bq is not None else None,
+                                          _p(bs) if bs is not None else None))
+        return (bq[:n] if bq is not None else None, bs[:n] if bs is not None else None)
+
+    def best_queries_device(self, d_scores: int, n: int, nq: int, d_best_query: int = 0,
+                            d_best_score: int = 0, min_score: Optional[int] = None,
+                            stream: int = 0):
+        """sw_best_queries_device: device pointers (ints); d_scores holds nq rows of n int32
+        scores, d_best_query (uint32) and d_best_score (int32) receive n entries each (either
+        may be 0).  Async on `stream` (0: the bank's own stream; sync() before reading)."""
+        self._check(lib().sw_best_queries_device(self._h, d_scores or None, n, nq,
+                                                 INT32_MIN if min_score is None else min_score,
+                                                 d_best_query or None, d_best_score or None,
+                                                 stream or None))
 
     # the k best hits of a score matrix
     def top_hits(self, scores: np.ndarray, k: int, ids: Optional[np.ndarray] = None,
