@@ -35,6 +35,9 @@
  *   sw_best_queries / sw_best_queries_device
  *       ≙ the same "best scores" question asked per target of a query set: which query hits
  *         this target best (the read-mapping shape, where the reads are the batch).
+ *   sw_estimate_statistics / sw_hit_significance (and their _device forms)
+ *       ≙ the "Statistics: (shuffled [500]) MLE statistics: Lambda= ...;  K=..." line and the
+ *         "bits" and "E(499)" columns of that report (data/alignments500.txt:13,19-21,24).
  *   sw_encode_ascii
  *       ≙ ConvertToBase (ScoreBank_v1_tb.sv:44-52): A=2 G=3 T=0 C=1 (lower case too);
  *         any other byte -> SW_DNA_N (4), which mismatches every code.
@@ -77,7 +80,10 @@ extern "C" {
  *        (test SWBANK_HAS_TOPK) the k best hits of a score matrix -- sw_top_hits,
  *        sw_top_hits_device; (test SWBANK_HAS_ALIGN_SET) alignments against a query set --
  *        sw_align_set_hits, sw_align_set_hits_device, SW_QUERY_NONE, SW_ALIGN_NO_HIT -- and the
- *        best query of every target -- sw_best_queries, sw_best_queries_device. */
+ *        best query of every target -- sw_best_queries, sw_best_queries_device; (test
+ *        SWBANK_HAS_STATS) hit significance -- sw_shuffle_batch_device,
+ *        sw_score_histogram_device, sw_fit_statistics, sw_estimate_statistics[_device],
+ *        sw_hit_significance[_device], sw_statistics. */
 #define SWBANK_ABI_VERSION 6
 #define SWBANK_HAS_ALIGN 1
 #define SWBANK_HAS_TOPK 1
@@ -489,6 +495,128 @@ sw_status sw_align_set_hits(sw_bank *bank, const uint8_t *residues, size_t resid
                             size_t n, const uint32_t *hit_queries, size_t hits_per_query,
                             const uint64_t *hits, size_t n_hits, sw_alignment *out,
                             uint32_t *cigar, size_t cigar_cap, size_t *cigar_used);
+
+/* ---- hit significance: shuffled-library statistics, bit scores, E-values (ABI 6 addition) ----
+ * The column of ssearch36's report that says how significant a hit is (the reference's
+ * data/alignments500.txt:13,19-21,24):
+ *     Statistics: (shuffled [500]) MLE statistics: Lambda= 0.1840;  K=0.1293
+ *     db211   ( 128) [f]   78 23.7    0.62
+ *      s-w opt:  78  Z-score: 97.7  bits: 23.7 E(499): 0.62
+ * ssearch36 scores the query against SHUFFLED library sequences and fits an extreme-value
+ * distribution to those scores; here the shuffle, the scoring pass and the score histogram run
+ * on the device over a batch that is already resident, only the histogram comes back, and the
+ * fit is a few thousand exp() on the host.  The chain of a search becomes
+ * score -> top hits -> significance -> align on one stream with no host step.
+ *
+ * The model: P(S < x) = exp(-K m n_t e^(-lambda x)) for a target of n_t codes against a query
+ * of m codes (the Gumbel law with the search space as the length correction), and for a hit
+ *     bits = (lambda S - ln K) / ln 2        E = db_size K m n_t e^(-lambda S)
+ * (db_size: the number of library sequences searched; with the reference's Lambda, K,
+ * 128 x 128 and db_size 499 these give the 23.7 / 0.62 and 22.1 / 1.9 the file prints).
+ *
+ * The shuffle of target k (position in the batch) under `seed`, in uint64 wrap-around
+ * arithmetic -- Fisher-Yates with a counter-based draw, so the result depends on (seed, k, the
+ * target's codes) alone, never on the grid, the slicing or the stream:
+ *     mix(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB;
+ *             z ^= z >> 31                      (the finaliser of splitmix64)
+ *     G = 0x9E3779B97F4A7C15;  key = mix(seed + G (k + 1));  out = in;
+ *     for j = L - 1 down to 1:  h = mix(key + G (j + 1));  r = ((h >> 32) (j + 1)) >> 32;
+ *                               swap out[j], out[r]
+ */
+#define SWBANK_HAS_STATS 1
+#define SW_STAT_BINS 4096              /* score bins of a histogram row: scores 0 .. 4095 */
+
+/* Device buffers, asynchronous on `stream` (NULL = the bank's): d_out[d_offsets[k] .. +d_lens[k])
+ * receives the shuffle of target k for every k < n (the batch as for sw_score_batch_device:
+ * targets at any byte offset, d_lens[k] may be 0, every d_lens[k] <= max_len); no other byte of
+ * d_out is written.  d_out must not overlap d_residues.  Neither penalties nor a query are
+ * needed; a multi-device bank runs it on its root.  SW_ERR_ARG: a NULL bank or buffer, n == 0,
+ * n >= 2^32.  sw_last_kernel reports "shuffle n=<n>". */
+sw_status sw_shuffle_batch_device(sw_bank *bank, const uint8_t *d_residues,
+                                  const uint64_t *d_offsets, const uint32_t *d_lens, size_t n,
+                                  uint32_t max_len, uint64_t seed, uint8_t *d_out, void *stream);
+
+/* Device buffers, asynchronous on `stream`: the score / length histogram of every row i of the
+ * nq x n score matrix (query-major, rows at any multiple of 4 bytes, as for sw_top_hits_device).
+ * With b = the score clamped into [0, SW_STAT_BINS - 1], every target adds 1 to
+ * d_counts[i * SW_STAT_BINS + b], d_lens[k] to d_len_sums[i * SW_STAT_BINS + b], and, when the
+ * clamp changed its score, 1 to d_clamped[i].  With d_lens, targets of length 0 are skipped
+ * everywhere.  d_lens and d_len_sums may both be NULL (a NULL d_lens skips nothing and sums
+ * nothing), d_clamped may be NULL.  The call ACCUMULATES into the caller's arrays, which the
+ * caller zeroes: several shuffle rounds and slices pool their counts.  All integers are exact,
+ * so the result does not depend on the order of arrival.  SW_ERR_ARG: a NULL bank, scores or
+ * counts; n or nq == 0; n > 2^32; nq * n or nq * SW_STAT_BINS overflowing size_t.
+ * sw_last_kernel reports "stat-hist nq=<nq> n=<n>". */
+sw_status sw_score_histogram_device(sw_bank *bank, const int32_t *d_scores, const uint32_t *d_lens,
+                                    size_t n, size_t nq, uint64_t *d_counts, uint64_t *d_len_sums,
+                                    uint64_t *d_clamped, void *stream);
+
+typedef struct sw_statistics {
+  double lambda, K;
+  uint64_t n_samples;         /* scores fitted (the non-empty targets over all rounds)      */
+  uint64_t n_clamped;         /* scores outside [0, SW_STAT_BINS - 1] (sw_estimate_* only)  */
+  uint32_t query_len, flags;
+  int32_t min_score, max_score; /* lowest and highest occupied bin (0 when there is none)   */
+} sw_statistics;
+enum { SW_STAT_DEGENERATE = 1, /* fewer than two distinct scores: lambda = K = 0            */
+       SW_STAT_CLAMPED = 2 };  /* a score was clamped into the histogram's range            */
+
+/* Host, no device: the maximum-likelihood lambda and K of one histogram row (SW_STAT_BINS
+ * counts and length sums, as sw_score_histogram_device writes them) for a query of query_len
+ * codes.  With c_s = counts[s], A_s = query_len * len_sums[s], N = sum c_s: lambda is the root of
+ *     1 / lambda - (sum s c_s) / N + (sum s A_s e^(-lambda s)) / (sum A_s e^(-lambda s))
+ * (strictly decreasing, so the root is unique; bracketed, solved until the relative change of
+ * lambda is <= 1e-13) and K = N / sum A_s e^(-lambda s).  Fewer than two occupied bins, N = 0 or
+ * query_len = 0: lambda = K = 0 and SW_STAT_DEGENERATE, the status still SW_OK.
+ * SW_ERR_ARG: a NULL argument. */
+sw_status sw_fit_statistics(const uint64_t *counts, const uint64_t *len_sums, uint32_t query_len,
+                            sw_statistics *out);
+
+/* The estimate.  For every round r < rounds (rounds >= 1): the batch is shuffled with seed
+ * seed + r into bank scratch, scored against the loaded query (every query of a loaded set)
+ * through sw_score_batch_device_range, and the scores go into one histogram row per query;
+ * after the last round the rows are copied back and fitted into out[0 .. sw_query_count()),
+ * host memory.  n_samples counts the non-empty targets over all rounds, SW_STAT_CLAMPED is set
+ * (and n_clamped counts) when a score left the histogram's range.  The work is enqueued on
+ * `stream` (NULL = the bank's) and the call returns after synchronising it: it hands a host
+ * struct back and runs once per query and library, not per batch.  The scratch (shuffled codes
+ * at a stride of max_len and nq x n scores) is bounded by SWBANK_STAT_MB (MiB, default 256); a
+ * batch past it runs in slices of targets, which cannot change a count, the shuffle being keyed
+ * by the batch position.  A multi-device bank scores as its scoring call does, shuffle and
+ * histogram on the root.  SW_ERR_STATE without penalties or a query; SW_ERR_ARG for a NULL
+ * bank, buffer or out, n == 0, n >= 2^32, rounds == 0, min_len > max_len; a latched hand-off
+ * fault is returned as by the other device calls.  sw_last_kernel reports
+ * "stats rounds=<r> nq=<nq> n=<n> slices=<s>". */
+sw_status sw_estimate_statistics_device(sw_bank *bank, const uint8_t *d_residues,
+                                        const uint64_t *d_offsets, const uint32_t *d_lens,
+                                        size_t n, uint32_t min_len, uint32_t max_len,
+                                        uint64_t seed, uint32_t rounds, sw_statistics *out,
+                                        void *stream);
+/* Host buffers, blocking: the batch as for sw_score_batch (a target outside the residues is
+ * SW_ERR_ARG); uploads it once and calls the device form. */
+sw_status sw_estimate_statistics(sw_bank *bank, const uint8_t *residues, size_t residues_len,
+                                 const uint64_t *offsets, const uint32_t *lens, size_t n,
+                                 uint64_t seed, uint32_t rounds, sw_statistics *out);
+
+/* Host, no device: bits[h] and evalues[h] (either may be NULL, not both) of n_hits hits with
+ * the given scores and target lengths.  SW_ERR_ARG: a NULL argument, both outputs NULL, or
+ * degenerate statistics (SW_STAT_DEGENERATE, lambda <= 0 or K <= 0). */
+sw_status sw_hit_significance(const sw_statistics *st, const int32_t *scores,
+                              const uint32_t *target_lens, size_t n_hits, uint64_t db_size,
+                              double *bits, double *evalues);
+/* Device buffers, asynchronous on `stream`: the nq x hits_per_query layout sw_top_hits_device
+ * writes -- d_hits[i * hits_per_query + j] a position into d_lens, d_hit_scores its score --
+ * with row i under st[i] (host memory, nq entries, read before the call returns).  A sentinel
+ * slot (SW_HIT_NONE) gets bits = -inf and E = +inf.  d_bits and d_evalues hold
+ * nq x hits_per_query doubles; either may be NULL, not both.  Runs on the root of a
+ * multi-device bank; calls on different streams are ordered by the bank.  SW_ERR_ARG as above,
+ * for any degenerate st[i], hits_per_query or nq == 0, or an overflowing product.
+ * sw_last_kernel reports "significance nq=<nq> k=<hits_per_query>". */
+sw_status sw_hit_significance_device(sw_bank *bank, const sw_statistics *st,
+                                     const int32_t *d_hit_scores, const uint64_t *d_hits,
+                                     const uint32_t *d_lens, size_t hits_per_query, size_t nq,
+                                     uint64_t db_size, double *d_bits, double *d_evalues,
+                                     void *stream);
 
 /* ---- profiling (≙ the CAPI AFU's cycle counters, capi_sample_aligner/hdl-verliog/afu.v
  *      _DEBUGGING_ "calculation #N completed, runtime: C cycles") ------------------------- */

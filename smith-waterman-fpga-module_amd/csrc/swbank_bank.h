@@ -5,7 +5,8 @@
 // host-buffer feeder and the host API), swbank_stream.hip (streamed host batches, one kernel
 // per call), swbank_multi.hip (multi-device banks and the RCCL gather), swbank_align.hip
 // (alignments of chosen hits, of one query or a query set), swbank_top.hip (the k best hits of
-// every row of a score matrix, the best query of every column).
+// every row of a score matrix, the best query of every column), swbank_stat.hip (hit
+// statistics: the seeded shuffle, the score histogram, the estimate, bits and E-values).
 #ifndef SWBANK_BANK_H
 #define SWBANK_BANK_H
 
@@ -111,6 +112,22 @@ extern "C" size_t swk_best_queries_keys(size_t n, size_t nq);
 extern "C" hipError_t swk_best_queries(const int32_t* scores, size_t n, size_t nq,
                                        int32_t min_score, unsigned long long* keys,
                                        uint32_t* best_query, int32_t* best_score, hipStream_t st);
+// swbank_kstat.hip: the seeded shuffle (stride == 0: into the caller's layout; else at a fixed
+// stride, the offsets written to out_offs), the score / length histogram (accumulating), bits
+// and E-values of a hit list (par: swk_stat_par_doubles() doubles per row)
+extern "C" hipError_t swk_shuffle_batch(const uint8_t* in, const uint64_t* offs,
+                                        const uint32_t* lens, size_t n, uint32_t max_len,
+                                        uint64_t k0, uint64_t seed, uint8_t* out,
+                                        uint64_t* out_offs, uint32_t stride, hipStream_t st);
+extern "C" hipError_t swk_stat_hist(const int32_t* scores, const uint32_t* lens, size_t n,
+                                    size_t nq, unsigned long long* counts,
+                                    unsigned long long* len_sums, unsigned long long* clamped,
+                                    hipStream_t st);
+extern "C" size_t swk_stat_par_doubles(void);
+extern "C" hipError_t swk_stat_signif(const double* par, const int32_t* hit_scores,
+                                      const uint64_t* hits, const uint32_t* lens, size_t k,
+                                      size_t nq, double db_size, double* bits, double* evalues,
+                                      hipStream_t st);
 
 // ---- helpers shared by the units ----------------------------------------------------
 inline int env_int(const char* name, int dflt) {
@@ -448,6 +465,18 @@ struct sw_bank {
   DevBuf<uint64_t> top_hits;
   DevBuf<uint32_t> top_cnt;
   hipEvent_t ev_top = nullptr;
+  // hit statistics (swbank_stat.hip): the estimate's shuffled codes, their offsets, the scores
+  // and the histogram rows (the call synchronises, so nothing outlives it); the host form's
+  // batch on the device; the significance call's per-row parameters, whose next upload waits
+  // for ev_stat (recorded after the kernel that reads them, on whichever stream it ran)
+  DevBuf<uint8_t> stat_codes, stat_hres;
+  DevBuf<uint64_t> stat_offs, stat_hoffs;
+  DevBuf<uint32_t> stat_hlens;
+  DevBuf<int32_t> stat_scores;
+  DevBuf<unsigned long long> stat_cnt;
+  DevBuf<double> stat_par;
+  std::vector<double> stat_hpar;  // (the upload's source, kept until ev_stat)
+  hipEvent_t ev_stat = nullptr;
   struct Seg { int W; size_t off, off16; };  // rows = W*R (last may be shorter); word offsets
                                               // in qtab and qtab16
   std::vector<Seg> segs;

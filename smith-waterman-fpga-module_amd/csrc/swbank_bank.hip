@@ -177,6 +177,7 @@ extern "C" void sw_bank_destroy(sw_bank* b) {
   (void)hipSetDevice(b->device);
   if (b->stream) (void)hipStreamSynchronize(b->stream);
   if (b->ev_top) (void)hipEventSynchronize(b->ev_top);  // the last top-hits call, on any stream
+  if (b->ev_stat) (void)hipEventSynchronize(b->ev_stat);  // ... significance call
   uint64_t nl;
   double pm, sm;
   (void)sw_bank_timing(b, &nl, &pm, &sm);
@@ -194,6 +195,7 @@ extern "C" void sw_bank_destroy(sw_bank* b) {
   if (b->ev_used) (void)hipEventDestroy(b->ev_used);
   if (b->best_ev) (void)hipEventDestroy(b->best_ev);
   if (b->ev_top) (void)hipEventDestroy(b->ev_top);
+  if (b->ev_stat) (void)hipEventDestroy(b->ev_stat);
   if (b->ev_join) (void)hipEventDestroy(b->ev_join);
   for (hipEvent_t e : b->deal_ev) (void)hipEventDestroy(e);
   b->fb_idx.release();
@@ -219,6 +221,14 @@ extern "C" void sw_bank_destroy(sw_bank* b) {
   b->top_hsc.release();
   b->top_hits.release();
   b->top_cnt.release();
+  b->stat_codes.release();
+  b->stat_hres.release();
+  b->stat_offs.release();
+  b->stat_hoffs.release();
+  b->stat_hlens.release();
+  b->stat_scores.release();
+  b->stat_cnt.release();
+  b->stat_par.release();
   b->dperm.release();
   b->dsort.release();
   b->bal_state.release();
@@ -356,6 +366,7 @@ extern "C" sw_status sw_bank_sync(sw_bank* b) {
   // ev_used follows every launch of a scoring call on the stream it ran on
   if (e == hipSuccess && b->ev_used) e = hipEventSynchronize(b->ev_used);
   if (e == hipSuccess && b->ev_top) e = hipEventSynchronize(b->ev_top);  // ... of a top-hits call
+  if (e == hipSuccess && b->ev_stat) e = hipEventSynchronize(b->ev_stat);  // ... significance
   if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
   (void)hipSetDevice(cur);
   HIPOK(b, e);

@@ -9,6 +9,7 @@
  *
  * Usage: swbank -q query.fa -l library.fa [-p match,mismatch,open,extend] [-P] [-g]
  *               [-d device[,device...]] [-o out.txt] [-T] [-R scores.txt] [-b] [-A k]
+ *               [-E rounds[,seed]] [-S lambda,K]
  *   -p  penalties (default 5,-4,-12,-4: ScoreBank_v1_tb.sv:16-19, data/smith-waterman.py:6-10)
  *   -P  protein mode (BLOSUM62; -p gives only open,extend)      -g  Gotoh gap model
  *   -T  testbench transcript format "@     0ns: %10s score: \t%d"
@@ -23,6 +24,12 @@
  *       summary line "Smith-Waterman score: S; P% identity (P% similar) in N nt overlap
  *       (qs-qe:ts-te)" with 1-based coordinates ("aa" with -P), then "cigar: ..." (a record
  *       scoring 0 prints the first two lines only)
+ *   -E  estimate lambda and K from `rounds` seeded shuffles of the library (seed 0 unless
+ *       given; sw_estimate_statistics, ≙ ssearch36's "Statistics: (shuffled [500]) MLE
+ *       statistics" line, data/alignments500.txt:13)      -S  take lambda and K as given
+ *       Either prints "Statistics: Lambda= L;  K=K (n samples)" after the score lines and extends
+ *       every hit's " s-w opt: S" line of -A to " s-w opt: S  bits: B E(n): E" with n = the
+ *       library's record count (data/alignments500.txt:24); without them nothing changes
  *   -b  also print the bank's best hit ("best: >name score: S", ≙ max / vld_max) to stderr
  * FASTA: '>' starts a record (name = first token); sequence lines are concatenated; CR/LF,
  * blank lines and lower case are accepted; bytes outside the alphabet encode to N (DNA) or X
@@ -110,7 +117,8 @@ fail:
 static void usage(const char *argv0) {
   fprintf(stderr,
           "usage: %s -q query.fa -l library.fa [-p match,mismatch,open,extend] [-P] [-g]\n"
-          "          [-d device[,device...]] [-o out.txt] [-T] [-R scores.txt] [-b] [-A k]\n",
+          "          [-d device[,device...]] [-o out.txt] [-T] [-R scores.txt] [-b] [-A k]\n"
+          "          [-E rounds[,seed]] [-S lambda,K]\n",
           argv0);
 }
 
@@ -125,7 +133,8 @@ static int by_score(const void *a, const void *b) {
 
 static int print_alignments(FILE *out, sw_bank *bank, const uint8_t *res, size_t total,
                             const uint64_t *offs, const uint32_t *lens, const int32_t *scores,
-                            const fasta_t *lib, size_t asked, const char *unit) {
+                            const fasta_t *lib, size_t asked, const char *unit,
+                            const sw_statistics *stats) {
   const size_t k = asked < lib->n ? asked : lib->n;
   const int on_device = asked <= SW_TOP_MAX_K; /* (what -A asked for picks the path) */
   uint64_t *order = malloc((on_device ? k : lib->n) * sizeof(uint64_t));
@@ -157,8 +166,13 @@ static int print_alignments(FILE *out, sw_bank *bank, const uint8_t *res, size_t
   } else {
     for (size_t i = 0; i < k; ++i) {
       const sw_alignment *a = &al[i];
-      fprintf(out, ">>%s (%u %s)\n s-w opt: %d\n", lib->names[a->index], lens[a->index], unit,
+      fprintf(out, ">>%s (%u %s)\n s-w opt: %d", lib->names[a->index], lens[a->index], unit,
               a->score);
+      double bits, ev;
+      if (stats && sw_hit_significance(stats, &a->score, &lens[a->index], 1, lib->n, &bits, &ev) ==
+                       SW_OK)
+        fprintf(out, "  bits: %.1f E(%zu): %.2g", bits, lib->n, ev);
+      fputc('\n', out);
       if (a->flags & SW_ALIGN_EMPTY) continue;
       if (a->flags == 0) {
         const double pct = 100.0 * a->n_identities / a->n_columns;
@@ -191,7 +205,12 @@ int main(int argc, char **argv) {
   int protein = 0, gotoh = 0, device = -1, transcript = 0, best = 0, opt;
   int ndev = 0, devs[SW_MAX_DEVICES];
   long nalign = 0;
-  while ((opt = getopt(argc, argv, "q:l:p:Pgd:o:TR:bA:h")) != -1) {
+  int have_stats = 0; /* 1: -S (given), 2: -E (estimated) */
+  unsigned long stat_rounds = 0;
+  unsigned long long stat_seed = 0;
+  sw_statistics stats;
+  memset(&stats, 0, sizeof(stats));
+  while ((opt = getopt(argc, argv, "q:l:p:Pgd:o:TR:bA:E:S:h")) != -1) {
     switch (opt) {
       case 'q': qpath = optarg; break;
       case 'l': lpath = optarg; break;
@@ -218,6 +237,25 @@ int main(int argc, char **argv) {
         if (end == optarg || *end || nalign < 0) return usage(argv[0]), 1;
         break;
       }
+      case 'E': {
+        char *end;
+        stat_rounds = strtoul(optarg, &end, 10);
+        if (end == optarg || stat_rounds == 0 || stat_rounds > 0xFFFFFFFFul) return usage(argv[0]), 1;
+        if (*end == ',') {
+          char *p = end + 1;
+          stat_seed = strtoull(p, &end, 10);
+          if (end == p) return usage(argv[0]), 1;
+        }
+        if (*end) return usage(argv[0]), 1;
+        have_stats = 2;
+        break;
+      }
+      case 'S':
+        if (sscanf(optarg, "%lf,%lf", &stats.lambda, &stats.K) != 2 || !(stats.lambda > 0) ||
+            !(stats.K > 0))
+          return usage(argv[0]), 1;
+        have_stats = 1;
+        break;
       case 'o': opath = optarg; break;
       case 'T': transcript = 1; break;
       case 'R': rpath = optarg; break;
@@ -293,6 +331,10 @@ int main(int argc, char **argv) {
     pos += l;
   }
   if (st == SW_OK) st = sw_score_batch(bank, res, total, offs, lens, NULL, lib.n, scores);
+  if (st == SW_OK && have_stats == 2 && lib.n)
+    st = sw_estimate_statistics(bank, res, total, offs, lens, lib.n, stat_seed,
+                                (uint32_t)stat_rounds, &stats);
+  if (have_stats == 1) stats.query_len = (uint32_t)qlen;
   if (st != SW_OK) {
     fprintf(stderr, "swbank: %s: %s\n", sw_status_string(st), sw_last_error(bank));
     sw_bank_destroy(bank);
@@ -311,9 +353,12 @@ int main(int argc, char **argv) {
     else
       fprintf(out, "%s score: %d\n", nm, scores[k]);
   }
+  if (have_stats)
+    fprintf(out, "Statistics: Lambda= %.4f;  K=%.4f (%llu samples)\n", stats.lambda, stats.K,
+            (unsigned long long)stats.n_samples);
   if (nalign > 0 && lib.n) {
     int rc = print_alignments(out, bank, res, total, offs, lens, scores, &lib, (size_t)nalign,
-                              protein ? "aa" : "nt");
+                              protein ? "aa" : "nt", have_stats ? &stats : NULL);
     if (rc) {
       if (opath) fclose(out);
       sw_bank_destroy(bank);

@@ -6,6 +6,7 @@
  *   charTo2bit     capi_sample_aligner/software-C,C++/include/aligner_Header.c:14-47
  *                  (2 bits per base, LSB first, 4 bases per byte; 'N' and other bytes -> 00b)
  */
+#include <math.h>
 #include <stdio.h>
 #include <string.h>
 
@@ -142,4 +143,85 @@ size_t sw_cigar_string(const uint32_t *ops, size_t n_ops, char *buf, size_t cap)
   }
   if (buf && cap) buf[need < cap ? need : cap - 1] = 0;
   return need;
+}
+
+/* ---- hit statistics (swbank.h "hit significance") --------------------------------------- */
+/* f(lambda) of the likelihood equations over the occupied bins [lo, hi], the exponent shifted
+ * by lo so nothing underflows; *sum receives sum A_s e^(-lambda (s - lo)). */
+static double stat_f(const uint64_t *counts, const uint64_t *len_sums, double m, int lo, int hi,
+                     double mean, double lambda, double *sum) {
+  double sa = 0.0, ssa = 0.0;
+  for (int s = lo; s <= hi; ++s) {
+    if (!counts[s]) continue;
+    const double w = m * (double)len_sums[s] * exp(-lambda * (double)(s - lo));
+    sa += w;
+    ssa += (double)s * w;
+  }
+  *sum = sa;
+  return 1.0 / lambda - mean + ssa / sa;
+}
+
+sw_status sw_fit_statistics(const uint64_t *counts, const uint64_t *len_sums, uint32_t query_len,
+                            sw_statistics *out) {
+  if (!counts || !len_sums || !out) return SW_ERR_ARG;
+  memset(out, 0, sizeof(*out));
+  out->query_len = query_len;
+  int lo = -1, hi = -1, bins = 0;
+  uint64_t N = 0;
+  double ssum = 0.0, wsum = 0.0;
+  for (int s = 0; s < SW_STAT_BINS; ++s) {
+    if (!counts[s]) continue;
+    if (lo < 0) lo = s;
+    hi = s;
+    ++bins;
+    N += counts[s];
+    ssum += (double)s * (double)counts[s];
+    wsum += (double)len_sums[s];
+  }
+  out->n_samples = N;
+  if (bins) {
+    out->min_score = lo;
+    out->max_score = hi;
+  }
+  /* (an occupied lowest bin without lengths has no weight: f need not change sign then) */
+  if (bins < 2 || query_len == 0 || wsum == 0.0 || len_sums[lo] == 0) {
+    out->flags = SW_STAT_DEGENERATE;
+    return SW_OK;
+  }
+  const double m = (double)query_len, mean = ssum / (double)N;
+  /* f is strictly decreasing from +inf to lo - mean < 0: bracket the root, then bisect */
+  double b = 1.0, sum;
+  while (b < 0x1p64 && stat_f(counts, len_sums, m, lo, hi, mean, b, &sum) > 0.0) b *= 2.0;
+  double a = 0.5 * b;
+  while (a > 0x1p-1000 && stat_f(counts, len_sums, m, lo, hi, mean, a, &sum) < 0.0) a *= 0.5;
+  if (b >= 0x1p64 || a <= 0x1p-1000) { /* no sign change found */
+    out->flags = SW_STAT_DEGENERATE;
+    return SW_OK;
+  }
+  for (int it = 0; it < 200 && b - a > 1e-13 * a; ++it) {
+    const double mid = 0.5 * (a + b);
+    if (stat_f(counts, len_sums, m, lo, hi, mean, mid, &sum) > 0.0) a = mid;
+    else b = mid;
+  }
+  const double lambda = 0.5 * (a + b);
+  (void)stat_f(counts, len_sums, m, lo, hi, mean, lambda, &sum);
+  out->lambda = lambda;
+  out->K = (double)N * exp(lambda * (double)lo) / sum;
+  return SW_OK;
+}
+
+sw_status sw_hit_significance(const sw_statistics *st, const int32_t *scores,
+                              const uint32_t *target_lens, size_t n_hits, uint64_t db_size,
+                              double *bits, double *evalues) {
+  if (!st || !scores || !target_lens || (!bits && !evalues)) return SW_ERR_ARG;
+  if ((st->flags & SW_STAT_DEGENERATE) || !(st->lambda > 0.0) || !(st->K > 0.0)) return SW_ERR_ARG;
+  const double ln_k = log(st->K);
+  for (size_t h = 0; h < n_hits; ++h) {
+    const double ls = st->lambda * (double)scores[h];
+    if (bits) bits[h] = (ls - ln_k) / 0.693147180559945309417232121458;
+    if (evalues)
+      evalues[h] = (double)db_size * st->K * (double)st->query_len * (double)target_lens[h] *
+                   exp(-ls);
+  }
+  return SW_OK;
 }

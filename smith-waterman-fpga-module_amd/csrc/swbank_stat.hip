@@ -1,0 +1,273 @@
+// swbank_stat.hip — hit statistics (include/swbank.h "hit significance"): the
+// ABI entries of the seeded shuffle, the score / length histogram, the estimate (shuffle ->
+// score -> histogram per round, then the host fit of swbank_host.c) and the significance of a
+// hit list.  The kernels are in swbank_kstat.hip; the scoring pass is the bank's own
+// sw_score_batch_device_range.
+#include "swbank_bank.h"
+
+namespace {
+
+// The bank whose device, stream and scratch a call uses: the root of a multi-device bank.
+sw_bank* root_of(sw_bank* b) { return b->is_multi() ? b->kids[0] : b; }
+
+// One launch group on `hs`, bracketed for sw_bank_set_timing like its siblings' (swbank_top.hip).
+template <class F>
+sw_status timed_on(sw_bank* b, hipStream_t hs, F&& f) {
+  Timed t{b, hs};
+  sw_status st = t.begin();
+  if (st != SW_OK) {
+    t.drop();
+    return st;
+  }
+  const hipError_t e = f();
+  if (e != hipSuccess) {
+    t.drop();
+    HIPOK(b, e);
+  }
+  if ((st = t.end()) != SW_OK) t.drop();
+  return st;
+}
+
+const char* bad_hist_args(const void* scores, const void* counts, size_t n, size_t nq) {
+  if (!scores || !counts) return "null scores or counts";
+  if (n == 0 || nq == 0) return "n and nq must be positive";
+  if (n > 0x100000000ull) return "a row holds <= 2^32 scores";
+  if (n > SIZE_MAX / sizeof(int32_t) / nq) return "nq x n overflows size_t";
+  if (nq > SIZE_MAX / (SW_STAT_BINS * sizeof(uint64_t))) return "nq x SW_STAT_BINS overflows size_t";
+  return nullptr;
+}
+
+bool degenerate(const sw_statistics& s) {
+  return (s.flags & SW_STAT_DEGENERATE) || !(s.lambda > 0.0) || !(s.K > 0.0);
+}
+
+}  // namespace
+
+extern "C" sw_status sw_shuffle_batch_device(sw_bank* b, const uint8_t* d_res,
+                                             const uint64_t* d_offs, const uint32_t* d_lens,
+                                             size_t n, uint32_t max_len, uint64_t seed,
+                                             uint8_t* d_out, void* stream) {
+  DevGuard dev_guard(b);  // on the bank's device; the caller's is restored on return (ABI 6)
+  if (!b) return SW_ERR_ARG;
+  if (!d_res || !d_offs || !d_lens || !d_out)
+    return fail(b, SW_ERR_ARG, "sw_shuffle_batch_device: null device buffer");
+  if (n == 0 || n >= 0x100000000ull)
+    return fail(b, SW_ERR_ARG, "sw_shuffle_batch_device: 0 < n < 2^32");
+  if (b->is_multi()) {  // on the root device
+    sw_bank* r = b->kids[0];
+    const sw_status st = sw_shuffle_batch_device(r, d_res, d_offs, d_lens, n, max_len, seed, d_out,
+                                                 stream ? stream : r->stream);
+    if (st != SW_OK) return fail(b, st, "device %d: %s", r->device, r->err);
+    snprintf(b->last_kernel, sizeof(b->last_kernel), "%s", r->last_kernel);
+    return SW_OK;
+  }
+  if (const sw_status fs = take_fault(b, 0); fs != SW_OK) return fs;
+  HIPOK(b, hipSetDevice(b->device));
+  hipStream_t hs = stream ? reinterpret_cast<hipStream_t>(stream) : b->stream;
+  const sw_status st = timed_on(b, hs, [&] {
+    return swk_shuffle_batch(d_res, d_offs, d_lens, n, max_len, 0, seed, d_out, nullptr, 0, hs);
+  });
+  if (st != SW_OK) return st;
+  snprintf(b->last_kernel, sizeof(b->last_kernel), "shuffle n=%zu", n);
+  return SW_OK;
+}
+
+extern "C" sw_status sw_score_histogram_device(sw_bank* b, const int32_t* d_scores,
+                                               const uint32_t* d_lens, size_t n, size_t nq,
+                                               uint64_t* d_counts, uint64_t* d_len_sums,
+                                               uint64_t* d_clamped, void* stream) {
+  DevGuard dev_guard(b);  // on the bank's device; the caller's is restored on return (ABI 6)
+  if (!b) return SW_ERR_ARG;
+  if (const char* why = bad_hist_args(d_scores, d_counts, n, nq))
+    return fail(b, SW_ERR_ARG, "sw_score_histogram_device: %s", why);
+  if (b->is_multi()) {  // on the root device, where the multi-device calls leave the scores
+    sw_bank* r = b->kids[0];
+    const sw_status st = sw_score_histogram_device(r, d_scores, d_lens, n, nq, d_counts,
+                                                   d_len_sums, d_clamped,
+                                                   stream ? stream : r->stream);
+    if (st != SW_OK) return fail(b, st, "device %d: %s", r->device, r->err);
+    snprintf(b->last_kernel, sizeof(b->last_kernel), "%s", r->last_kernel);
+    return SW_OK;
+  }
+  if (const sw_status fs = take_fault(b, 0); fs != SW_OK) return fs;
+  HIPOK(b, hipSetDevice(b->device));
+  hipStream_t hs = stream ? reinterpret_cast<hipStream_t>(stream) : b->stream;
+  const sw_status st = timed_on(b, hs, [&] {
+    return swk_stat_hist(d_scores, d_lens, n, nq, reinterpret_cast<unsigned long long*>(d_counts),
+                         reinterpret_cast<unsigned long long*>(d_len_sums),
+                         reinterpret_cast<unsigned long long*>(d_clamped), hs);
+  });
+  if (st != SW_OK) return st;
+  snprintf(b->last_kernel, sizeof(b->last_kernel), "stat-hist nq=%zu n=%zu", nq, n);
+  return SW_OK;
+}
+
+extern "C" sw_status sw_estimate_statistics_device(sw_bank* b, const uint8_t* d_res,
+                                                   const uint64_t* d_offs, const uint32_t* d_lens,
+                                                   size_t n, uint32_t min_len, uint32_t max_len,
+                                                   uint64_t seed, uint32_t rounds,
+                                                   sw_statistics* out, void* stream) {
+  DevGuard dev_guard(b);  // on the bank's device; the caller's is restored on return (ABI 6)
+  if (!b) return SW_ERR_ARG;
+  if (!d_res || !d_offs || !d_lens || !out)
+    return fail(b, SW_ERR_ARG, "sw_estimate_statistics_device: null buffer");
+  if (n == 0 || n >= 0x100000000ull || rounds == 0)
+    return fail(b, SW_ERR_ARG, "sw_estimate_statistics_device: 0 < n < 2^32 and rounds >= 1");
+  if (min_len > max_len) return fail(b, SW_ERR_ARG, "min_len %u > max_len %u", min_len, max_len);
+  sw_bank* r = root_of(b);
+  if (!r->have_pen || !b->have_query)
+    return fail(b, SW_ERR_STATE, "penalties or query not loaded");
+  // a hand-off fault latched by an earlier device call is returned before anything runs
+  if (const sw_status fs = take_fault(b, 0); fs != SW_OK) return fs;
+  const size_t nq = sw_query_count(b);
+  HIPOK(b, hipSetDevice(r->device));
+  hipStream_t hs = stream ? reinterpret_cast<hipStream_t>(stream) : r->stream;
+  // a slice of targets: its shuffled codes at a fixed stride, its offsets, nq rows of scores
+  const size_t stride = ((size_t)max_len + 15) / 16 * 16 + 16;
+  if (stride > UINT32_MAX) return fail(b, SW_ERR_ARG, "max_len %u too long", max_len);
+  const size_t per = stride + sizeof(uint64_t) + nq * sizeof(int32_t);
+  const size_t budget = (size_t)std::max(1, env_int("SWBANK_STAT_MB", 256)) << 20;
+  const size_t span = std::min(n, std::max<size_t>(1, budget / per));
+  const size_t slices = (n + span - 1) / span;
+  const size_t row = (size_t)SW_STAT_BINS, words = nq * (2 * row + 1);  // counts, sums, clamped
+  // (the stride's padding is never written: zeroed once, so whatever a score kernel reads past
+  // a target's end is a code of the alphabet, as in a caller's packed batch)
+  if (r->stat_codes.cap < span * stride + 64) {
+    HIPOK(b, r->stat_codes.reserve(span * stride + 64));
+    HIPOK(b, hipMemsetAsync(r->stat_codes.p, 0, r->stat_codes.cap, hs));
+  }
+  HIPOK(b, r->stat_offs.reserve(span));
+  HIPOK(b, r->stat_scores.reserve(span * nq));
+  HIPOK(b, r->stat_cnt.reserve(words));
+  unsigned long long* counts = r->stat_cnt.p;
+  unsigned long long* sums = counts + nq * row;
+  unsigned long long* clamped = sums + nq * row;
+  HIPOK(b, hipMemsetAsync(counts, 0, words * sizeof(*counts), hs));
+  for (uint32_t rd = 0; rd < rounds; ++rd) {
+    for (size_t k0 = 0; k0 < n; k0 += span) {
+      const size_t nk = std::min(span, n - k0);
+      HIPOK(b, swk_shuffle_batch(d_res, d_offs + k0, d_lens + k0, nk, max_len, k0, seed + rd,
+                                 r->stat_codes.p, r->stat_offs.p, (uint32_t)stride, hs));
+      const sw_status st =
+          sw_score_batch_device_range(b, r->stat_codes.p, r->stat_offs.p, d_lens + k0, nullptr, nk,
+                                      min_len, max_len, r->stat_scores.p, hs);
+      if (st != SW_OK) {
+        (void)hipStreamSynchronize(hs);  // (nothing of the call is left in flight)
+        return st;
+      }
+      HIPOK(b, hipSetDevice(r->device));
+      HIPOK(b, swk_stat_hist(r->stat_scores.p, d_lens + k0, nk, nq, counts, sums, clamped, hs));
+    }
+  }
+  std::vector<unsigned long long> host(words);
+  HIPOK(b, hipMemcpyAsync(host.data(), counts, words * sizeof(*counts), hipMemcpyDeviceToHost,
+                          hs));
+  HIPOK(b, hipStreamSynchronize(hs));
+  // the scoring passes' hand-off faults: their scores, and so the counts, are invalid
+  if (const sw_status fs = take_fault(b, 0); fs != SW_OK) return fs;
+  const sw_bank* src = r;  // (the root of a multi-device bank holds the queries)
+  for (size_t i = 0; i < nq; ++i) {
+    const size_t qlen = src->qset.size() > 1 ? src->qset[i].size() : src->query.size();
+    const sw_status st = sw_fit_statistics(reinterpret_cast<const uint64_t*>(host.data() + i * row),
+                                           reinterpret_cast<const uint64_t*>(host.data() + (nq + i) * row),
+                                           (uint32_t)qlen, &out[i]);
+    if (st != SW_OK) return fail(b, st, "sw_fit_statistics failed for query %zu", i);
+    out[i].n_clamped = host[2 * nq * row + i];
+    if (out[i].n_clamped) out[i].flags |= SW_STAT_CLAMPED;
+  }
+  snprintf(b->last_kernel, sizeof(b->last_kernel), "stats rounds=%u nq=%zu n=%zu slices=%zu",
+           rounds, nq, n, slices);
+  return SW_OK;
+}
+
+extern "C" sw_status sw_estimate_statistics(sw_bank* b, const uint8_t* residues,
+                                            size_t residues_len, const uint64_t* offsets,
+                                            const uint32_t* lens, size_t n, uint64_t seed,
+                                            uint32_t rounds, sw_statistics* out) {
+  DevGuard dev_guard(b);  // on the bank's device; the caller's is restored on return (ABI 6)
+  if (!b) return SW_ERR_ARG;
+  if (!residues || !offsets || !lens || !out)
+    return fail(b, SW_ERR_ARG, "sw_estimate_statistics: null buffer");
+  if (n == 0 || n >= 0x100000000ull || rounds == 0)
+    return fail(b, SW_ERR_ARG, "sw_estimate_statistics: 0 < n < 2^32 and rounds >= 1");
+  sw_bank* r = root_of(b);
+  if (!r->have_pen || !b->have_query)
+    return fail(b, SW_ERR_STATE, "penalties or query not loaded");
+  uint32_t lo = UINT32_MAX, hi = 0;
+  for (size_t k = 0; k < n; ++k) {
+    if (offsets[k] > residues_len || lens[k] > residues_len - offsets[k])
+      return fail(b, SW_ERR_ARG, "target %zu lies outside the %zu residues", k, residues_len);
+    lo = std::min(lo, lens[k]);
+    hi = std::max(hi, lens[k]);
+  }
+  HIPOK(b, hipSetDevice(r->device));
+  hipStream_t hs = r->stream;
+  HIPOK(b, r->stat_hres.reserve(residues_len + 64));
+  HIPOK(b, r->stat_hoffs.reserve(n));
+  HIPOK(b, r->stat_hlens.reserve(n));
+  if (residues_len)
+    HIPOK(b, hipMemcpyAsync(r->stat_hres.p, residues, residues_len, hipMemcpyHostToDevice, hs));
+  HIPOK(b, hipMemcpyAsync(r->stat_hoffs.p, offsets, n * sizeof(uint64_t), hipMemcpyHostToDevice,
+                          hs));
+  HIPOK(b, hipMemcpyAsync(r->stat_hlens.p, lens, n * sizeof(uint32_t), hipMemcpyHostToDevice, hs));
+  const sw_status st = sw_estimate_statistics_device(b, r->stat_hres.p, r->stat_hoffs.p,
+                                                     r->stat_hlens.p, n, lo, hi, seed, rounds, out,
+                                                     hs);
+  if (st != SW_OK) (void)hipStreamSynchronize(hs);  // (the uploads have left the caller's buffers)
+  return st;
+}
+
+extern "C" sw_status sw_hit_significance_device(sw_bank* b, const sw_statistics* st,
+                                                const int32_t* d_hit_scores, const uint64_t* d_hits,
+                                                const uint32_t* d_lens, size_t hits_per_query,
+                                                size_t nq, uint64_t db_size, double* d_bits,
+                                                double* d_evalues, void* stream) {
+  DevGuard dev_guard(b);  // on the bank's device; the caller's is restored on return (ABI 6)
+  if (!b) return SW_ERR_ARG;
+  if (!st || !d_hit_scores || !d_hits || !d_lens || (!d_bits && !d_evalues))
+    return fail(b, SW_ERR_ARG, "sw_hit_significance_device: null argument, or neither output");
+  if (hits_per_query == 0 || nq == 0)
+    return fail(b, SW_ERR_ARG, "sw_hit_significance_device: hits_per_query and nq must be positive");
+  const size_t pw = swk_stat_par_doubles();
+  if (hits_per_query > SIZE_MAX / sizeof(uint64_t) / nq || nq > SIZE_MAX / (pw * sizeof(double)))
+    return fail(b, SW_ERR_ARG, "sw_hit_significance_device: nq x hits_per_query overflows size_t");
+  for (size_t i = 0; i < nq; ++i)
+    if (degenerate(st[i]))
+      return fail(b, SW_ERR_ARG, "sw_hit_significance_device: degenerate statistics (row %zu)", i);
+  if (b->is_multi()) {  // on the root device
+    sw_bank* r = b->kids[0];
+    const sw_status s = sw_hit_significance_device(r, st, d_hit_scores, d_hits, d_lens,
+                                                   hits_per_query, nq, db_size, d_bits, d_evalues,
+                                                   stream ? stream : r->stream);
+    if (s != SW_OK) return fail(b, s, "device %d: %s", r->device, r->err);
+    snprintf(b->last_kernel, sizeof(b->last_kernel), "%s", r->last_kernel);
+    return SW_OK;
+  }
+  if (const sw_status fs = take_fault(b, 0); fs != SW_OK) return fs;
+  HIPOK(b, hipSetDevice(b->device));
+  hipStream_t hs = stream ? reinterpret_cast<hipStream_t>(stream) : b->stream;
+  // the previous call's upload and kernel (on any stream) are done with the parameters, on the
+  // host and on the device, before they are replaced: a short host wait for a small kernel
+  if (!b->ev_stat) HIPOK(b, hipEventCreateWithFlags(&b->ev_stat, hipEventDisableTiming));
+  else HIPOK(b, hipEventSynchronize(b->ev_stat));
+  std::vector<double>& par = b->stat_hpar;
+  par.assign(nq * pw, 0.0);
+  for (size_t i = 0; i < nq; ++i) {
+    par[i * pw + 0] = st[i].lambda;
+    par[i * pw + 1] = st[i].K;
+    par[i * pw + 2] = (double)st[i].query_len;
+    par[i * pw + 3] = std::log(st[i].K);
+  }
+  HIPOK(b, b->stat_par.reserve(par.size()));
+  HIPOK(b, hipMemcpyAsync(b->stat_par.p, par.data(), par.size() * sizeof(double),
+                          hipMemcpyHostToDevice, hs));
+  const sw_status s = timed_on(b, hs, [&] {
+    return swk_stat_signif(b->stat_par.p, d_hit_scores, d_hits, d_lens, hits_per_query, nq,
+                           (double)db_size, d_bits, d_evalues, hs);
+  });
+  const hipError_t er = hipEventRecord(b->ev_stat, hs);
+  if (s != SW_OK) return s;
+  HIPOK(b, er);
+  snprintf(b->last_kernel, sizeof(b->last_kernel), "significance nq=%zu k=%zu", nq, hits_per_query);
+  return SW_OK;
+}

@@ -49,6 +49,9 @@ EXPORTS = (
     "sw_top_hits", "sw_top_hits_device",
     "sw_best_queries", "sw_best_queries_device",
     "sw_align_set_hits", "sw_align_set_hits_device",
+    "sw_shuffle_batch_device", "sw_score_histogram_device", "sw_fit_statistics",
+    "sw_estimate_statistics", "sw_estimate_statistics_device",
+    "sw_hit_significance", "sw_hit_significance_device",
 )
 ABI_VERSION = 6
 COUNTERS = ("stream_calls", "stream_reruns", "stream_declined", "chunked_calls", "device_sorts",
@@ -64,6 +67,8 @@ TOP_MAX_K = 4096                             # SW_TOP_MAX_K: the largest k of th
 HIT_NONE = 0xFFFFFFFFFFFFFFFF                # SW_HIT_NONE: a hit slot past the row's count
 QUERY_NONE = 0xFFFFFFFF                      # SW_QUERY_NONE: "no query" in a hit-query list
 INT32_MIN = -(1 << 31)                       # min_score: no threshold; the score of such a slot
+STAT_BINS = 4096                             # SW_STAT_BINS: score bins of a histogram row
+STAT_DEGENERATE, STAT_CLAMPED = 1, 2         # sw_statistics.flags
 
 
 class SwbankError(RuntimeError):
@@ -88,6 +93,27 @@ class AlignmentRecord(ctypes.Structure):
                 ("t_end", ctypes.c_uint32), ("n_columns", ctypes.c_uint32),
                 ("n_identities", ctypes.c_uint32), ("cigar_offset", ctypes.c_uint32),
                 ("cigar_len", ctypes.c_uint32)]
+
+
+class Statistics(ctypes.Structure):
+    """sw_statistics: lambda and K of one query's shuffled-library fit (48 bytes)."""
+    _fields_ = [("lambda_", ctypes.c_double), ("K", ctypes.c_double),
+                ("n_samples", ctypes.c_uint64), ("n_clamped", ctypes.c_uint64),
+                ("query_len", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+                ("min_score", ctypes.c_int32), ("max_score", ctypes.c_int32)]
+
+    @property
+    def degenerate(self) -> bool:
+        return bool(self.flags & STAT_DEGENERATE)
+
+    @property
+    def clamped(self) -> bool:
+        return bool(self.flags & STAT_CLAMPED)
+
+    def __repr__(self):
+        return (f"Statistics(lambda_={self.lambda_!r}, K={self.K!r}, n_samples={self.n_samples}, "
+                f"n_clamped={self.n_clamped}, query_len={self.query_len}, flags={self.flags}, "
+                f"min_score={self.min_score}, max_score={self.max_score})")
 
 
 ALIGNMENT_DTYPE = np.dtype([(n, np.dtype(t)) for n, t in AlignmentRecord._fields_])
@@ -218,6 +244,13 @@ def lib() -> ctypes.CDLL:
         "sw_best_queries_device": (i32, [P, P, sz, sz, i32, P, P, P]),
         "sw_align_set_hits": (i32, [P, P, sz, P, P, P, sz, P, sz, P, sz, P, P, sz, P]),
         "sw_align_set_hits_device": (i32, [P, P, P, P, P, sz, u32, P, sz, P, sz, P, P, u32, P]),
+        "sw_shuffle_batch_device": (i32, [P, P, P, P, sz, u32, u64, P, P]),
+        "sw_score_histogram_device": (i32, [P, P, P, sz, sz, P, P, P, P]),
+        "sw_fit_statistics": (i32, [P, P, u32, P]),
+        "sw_estimate_statistics_device": (i32, [P, P, P, P, sz, u32, u32, u64, u32, P, P]),
+        "sw_estimate_statistics": (i32, [P, P, sz, P, P, sz, u64, u32, P]),
+        "sw_hit_significance": (i32, [P, P, P, sz, u64, P, P]),
+        "sw_hit_significance_device": (i32, [P, P, P, P, P, sz, sz, u64, P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -334,6 +367,43 @@ def validate_batch(residues, offsets, lens, ids=None):
         if idv.size != ln.size:
             raise ValueError(f"{idv.size} ids for {ln.size} targets")
     return res, offs, ln, idv
+
+
+# ---- hit statistics on the host (no device) -----------------------------------------------
+def fit_statistics(counts, len_sums, query_len: int) -> Statistics:
+    """sw_fit_statistics: the maximum-likelihood lambda and K of one histogram row (STAT_BINS
+    counts and length sums, as score_histogram_device writes them)."""
+    c = np.ascontiguousarray(counts, dtype=np.uint64).reshape(-1)
+    ls = np.ascontiguousarray(len_sums, dtype=np.uint64).reshape(-1)
+    if c.size != STAT_BINS or ls.size != STAT_BINS:
+        raise ValueError(f"a histogram row holds {STAT_BINS} bins")
+    out = Statistics()
+    st = lib().sw_fit_statistics(_p(c), _p(ls), query_len, ctypes.byref(out))
+    if st != OK:
+        raise SwbankError(st, status_string(st))
+    return out
+
+
+def make_statistics(lambda_: float, K: float, query_len: int) -> Statistics:
+    """Given statistics (e.g. the Lambda and K another tool printed) for hit_significance."""
+    return Statistics(lambda_=lambda_, K=K, query_len=query_len)
+
+
+def hit_significance(stats: Statistics, scores, target_lens, db_size: int):
+    """sw_hit_significance: (bits float64 [n], evalues float64 [n]) of hits with the given
+    scores and target lengths in a library of db_size sequences."""
+    sc = np.ascontiguousarray(scores, dtype=np.int32).reshape(-1)
+    tl = np.ascontiguousarray(target_lens, dtype=np.uint32).reshape(-1)
+    if sc.size != tl.size:
+        raise ValueError(f"{sc.size} scores for {tl.size} target lengths")
+    bits = np.empty(max(sc.size, 1), np.float64)
+    ev = np.empty(max(sc.size, 1), np.float64)
+    st = lib().sw_hit_significance(ctypes.byref(stats), _p(sc) if sc.size else _p(bits),
+                                   _p(tl) if tl.size else _p(bits), sc.size, db_size, _p(bits),
+                                   _p(ev))
+    if st != OK:
+        raise SwbankError(st, status_string(st))
+    return bits[:sc.size], ev[:sc.size]
 
 
 # ---- the bank ----------------------------------------------------------------------------
@@ -638,6 +708,60 @@ class ScoreBank:
                                              INT32_MIN if min_score is None else min_score,
                                              d_hits or None, d_hit_scores or None,
                                              d_hit_ids or None, d_counts or None, stream or None))
+
+    # hit statistics: shuffle, histogram, estimate, significance
+    def shuffle_batch_device(self, d_res: int, d_offs: int, d_lens: int, n: int, max_len: int,
+                             seed: int, d_out: int, stream: int = 0):
+        """sw_shuffle_batch_device: device pointers (ints); d_out[d_offs[k] .. + d_lens[k])
+        receives the seeded shuffle of target k, nothing else of d_out is written.  Async on
+        `stream` (0: the bank's own stream; sync() before reading)."""
+        self._check(lib().sw_shuffle_batch_device(self._h, d_res or None, d_offs or None,
+                                                  d_lens or None, n, max_len, seed,
+                                                  d_out or None, stream or None))
+
+    def score_histogram_device(self, d_scores: int, n: int, d_counts: int, nq: int = 1,
+                               d_lens: int = 0, d_len_sums: int = 0, d_clamped: int = 0,
+                               stream: int = 0):
+        """sw_score_histogram_device: device pointers (ints); adds the score / length histogram
+        of every row of d_scores [nq, n] to d_counts and d_len_sums (uint64 [nq, STAT_BINS]) and
+        the clamped scores to d_clamped (uint64 [nq]); the caller zeroes them.  Async."""
+        self._check(lib().sw_score_histogram_device(self._h, d_scores or None, d_lens or None, n,
+                                                    nq, d_counts or None, d_len_sums or None,
+                                                    d_clamped or None, stream or None))
+
+    def estimate_statistics_device(self, d_res: int, d_offs: int, d_lens: int, n: int,
+                                   max_len: int, seed: int = 0, rounds: int = 1,
+                                   min_len: int = 0, stream: int = 0) -> list:
+        """sw_estimate_statistics_device: one Statistics per loaded query from `rounds` shuffles
+        of the device batch (seeds seed .. seed + rounds - 1).  Returns after synchronising."""
+        out = (Statistics * max(self.query_count(), 1))()
+        self._check(lib().sw_estimate_statistics_device(self._h, d_res or None, d_offs or None,
+                                                        d_lens or None, n, min_len, max_len, seed,
+                                                        rounds, out, stream or None))
+        return list(out)[:self.query_count()]
+
+    def estimate_statistics(self, residues: np.ndarray, offsets: np.ndarray, lens: np.ndarray,
+                            seed: int = 0, rounds: int = 1) -> list:
+        """sw_estimate_statistics: the same for a host batch (uploaded once)."""
+        res, offs, ln, _ = validate_batch(residues, offsets, lens)
+        out = (Statistics * max(self.query_count(), 1))()
+        self._check(lib().sw_estimate_statistics(self._h, _p(res), res.size, _p(offs), _p(ln),
+                                                 len(ln), seed, rounds, out))
+        return list(out)[:self.query_count()]
+
+    def hit_significance_device(self, stats, d_hit_scores: int, d_hits: int, d_lens: int,
+                                hits_per_query: int, db_size: int, d_bits: int = 0,
+                                d_evalues: int = 0, stream: int = 0):
+        """sw_hit_significance_device: device pointers (ints); stats one Statistics per row of the
+        [nq, hits_per_query] layout top_hits_device writes; d_bits / d_evalues (float64, either
+        may be 0) receive bits and E-values, -inf / +inf in a HIT_NONE slot.  Async."""
+        stats = [stats] if isinstance(stats, Statistics) else list(stats)
+        arr = (Statistics * max(len(stats), 1))(*stats)
+        self._check(lib().sw_hit_significance_device(self._h, arr, d_hit_scores or None,
+                                                     d_hits or None, d_lens or None,
+                                                     hits_per_query, len(stats), db_size,
+                                                     d_bits or None, d_evalues or None,
+                                                     stream or None))
 
     def counters(self) -> dict:
         """sw_bank_counters: feeder / fallback counts since the bank was created."""
