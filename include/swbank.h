@@ -38,6 +38,10 @@
  *   sw_estimate_statistics / sw_hit_significance (and their _device forms)
  *       ≙ the "Statistics: (shuffled [500]) MLE statistics: Lambda= ...;  K=..." line and the
  *         "bits" and "E(499)" columns of that report (data/alignments500.txt:13,19-21,24).
+ *   sw_score_strands / sw_align_strand_hits (and their _device forms)
+ *       ≙ the "[f]" column of that report: the reference ran ssearch36 -3 (forward strand only,
+ *         data/alignments500.txt:1); without -3 a DNA search scores both strands and prints
+ *         [f] or [r] per hit.
  *   sw_encode_ascii
  *       ≙ ConvertToBase (ScoreBank_v1_tb.sv:44-52): A=2 G=3 T=0 C=1 (lower case too);
  *         any other byte -> SW_DNA_N (4), which mismatches every code.
@@ -83,7 +87,9 @@ extern "C" {
  *        best query of every target -- sw_best_queries, sw_best_queries_device; (test
  *        SWBANK_HAS_STATS) hit significance -- sw_shuffle_batch_device,
  *        sw_score_histogram_device, sw_fit_statistics, sw_estimate_statistics[_device],
- *        sw_hit_significance[_device], sw_statistics. */
+ *        sw_hit_significance[_device], sw_statistics; (test SWBANK_HAS_STRANDS) both DNA
+ *        strands -- sw_revcomp_codes, sw_revcomp_batch_device, sw_score_strands[_device],
+ *        sw_align_strand_hits[_device], SW_ALIGN_REVERSE. */
 #define SWBANK_ABI_VERSION 6
 #define SWBANK_HAS_ALIGN 1
 #define SWBANK_HAS_TOPK 1
@@ -617,6 +623,108 @@ sw_status sw_hit_significance_device(sw_bank *bank, const sw_statistics *st,
                                      const uint32_t *d_lens, size_t hits_per_query, size_t nq,
                                      uint64_t db_size, double *d_bits, double *d_evalues,
                                      void *stream);
+
+/* ---- both DNA strands (ABI 6 addition) --------------------------------------------------------
+ * The "[f]" column of ssearch36's report (the reference's data/alignments500.txt:19-21,
+ * "db211 ( 128) [f] 78 23.7 0.62").  The reference ran `ssearch36 -3`, which turns the reverse
+ * strand off; every DNA search tool searches both strands by default, and these calls do.
+ *
+ * Definitions:
+ *   rc        the reverse complement of a target: the codes in reverse order, each mapped
+ *             T <-> A (0 <-> 2) and C <-> G (1 <-> 3), i.e. c < 4 ? c ^ 2 : c.  N stays N.
+ *   reverse   the reverse-strand score of (query, target) is what the bank returns for
+ *             (query, rc(target)).  That is exact by construction under every gap model and
+ *             matrix the bank accepts; no reversal-symmetry argument is needed.
+ *   ssearch36 searches the reverse strand as (rc(query), target).  Under SW_GAP_GOTOH, or
+ *             SW_GAP_MERGED penalties without the first-column case (max(s) <= open + extend),
+ *             and a complement-symmetric matrix (s(a, b) = s(comp a, comp b), as every
+ *             match / mismatch matrix is), the two are the same number: an alignment of
+ *             (q, rc(t)) read backwards and complemented is an alignment of (rc(q), t) with the
+ *             same columns and the same gap runs (tests/test_strand_cases.py pins it on the
+ *             reference's data500: 0 of 499 targets differ, both gap models).
+ *   merged    score = max(forward, reverse); the strand is 1 only when the reverse score is
+ *             strictly greater.  A tie is the forward strand -- "lowest index wins", as
+ *             everywhere else.
+ *   alphabet  DNA banks only: every call below returns SW_ERR_UNSUPPORTED on a protein bank.
+ */
+#define SWBANK_HAS_STRANDS 1
+
+/* Host, no device: out[0..n) = rc(codes[0..n)); out may be codes itself (in place), any other
+ * overlap is not allowed.  Returns n (0 for a NULL argument). */
+size_t sw_revcomp_codes(const uint8_t *codes, size_t n, uint8_t *out);
+
+/* Device buffers, asynchronous on `stream` (NULL = the bank's): d_out[d_offsets[k] .. +d_lens[k])
+ * receives rc of target k for every k < n (the batch as for sw_score_batch_device: targets at any
+ * byte offset, d_lens[k] may be 0); no other byte of d_out is written.  d_out must not overlap
+ * d_residues.  Neither penalties nor a query are needed; a multi-device bank runs it on its root.
+ * A library is complemented once and handed to sw_score_strands_device for every query.
+ * SW_ERR_ARG: a NULL bank or buffer, n == 0, n >= 2^32.  sw_last_kernel reports
+ * "revcomp n=<n>". */
+sw_status sw_revcomp_batch_device(sw_bank *bank, const uint8_t *d_residues,
+                                  const uint64_t *d_offsets, const uint32_t *d_lens, size_t n,
+                                  uint8_t *d_out, void *stream);
+
+/* Device buffers, asynchronous on `stream`: scores the batch on both strands against the loaded
+ * query or query set.  With nq = sw_query_count(): d_scores receives the merged nq x n int32
+ * scores, query-major; d_strands (may be NULL) the nq x n uint8 strands.  Each strand goes
+ * through sw_score_batch_device_range exactly as a forward search does -- a single query stays
+ * on the single-query kernels; kernel choice, the int32 re-score, balanced ranges and
+ * multi-device dealing are unchanged -- and a merge kernel follows.
+ *   d_rc given  the caller's resident reverse complement (sw_revcomp_batch_device), target k at
+ *               d_rc + d_offsets[k].
+ *   d_rc NULL   the bank makes it in its own scratch.  The scratch (rc codes at a stride of
+ *               max_len, plus the reverse scores) is bounded by SWBANK_STRAND_MB (MiB, default
+ *               256); a batch past the bound runs in slices of targets, which cannot change a
+ *               result.
+ * No best hit is tracked (sw_batch_best: SW_ERR_STATE).  A latched hand-off fault of an earlier
+ * device call is returned as by the other device calls; sw_bank_sync waits for the merge.
+ * SW_ERR_STATE without penalties or a query; SW_ERR_ARG for min_len > max_len, a NULL buffer
+ * (n > 0) or n >= 2^32; n == 0 is SW_OK.  sw_last_kernel reports
+ * "strands nq=<nq> n=<n> slices=<s>"; with sw_bank_set_timing the rc pass and the merge are
+ * each bracketed as one launch (per slice), beside the scoring passes' own. */
+sw_status sw_score_strands_device(sw_bank *bank, const uint8_t *d_residues, const uint8_t *d_rc,
+                                  const uint64_t *d_offsets, const uint32_t *d_lens, size_t n,
+                                  uint32_t min_len, uint32_t max_len, int32_t *d_scores,
+                                  uint8_t *d_strands, void *stream);
+
+/* Host buffers, blocking; the batch as for sw_score_batch (a target outside the residues or a
+ * code outside the alphabet is SW_ERR_ARG): uploads it once and calls the device form with
+ * d_rc = NULL.  scores_out: nq x n; strands_out: nq x n, may be NULL. */
+sw_status sw_score_strands(sw_bank *bank, const uint8_t *residues, size_t residues_len,
+                           const uint64_t *offsets, const uint32_t *lens, size_t n,
+                           int32_t *scores_out, uint8_t *strands_out);
+
+/* sw_align_set_hits[_device] with one more argument, the nq x n strand matrix sw_score_strands
+ * writes (a single loaded query is a set of one): hit h (query i, target k) is aligned against
+ * rc(target k) when strands[i * n + k] != 0.  strands == NULL equals sw_align_set_hits[_device]
+ * byte for byte.  No reverse complement is taken or needed: a reverse hit reads its target from
+ * the far end under a column-complemented matrix.
+ *
+ * The record of a reverse hit: every rule above (end, start, CIGAR preference, empty pair,
+ * SW_ALIGN_NO_PATH, budget, chunks) holds on the reverse-complemented target, so it is record
+ * for record what sw_align_set_hits returns for a batch holding rc(target), except that
+ *   flags |= SW_ALIGN_REVERSE (an empty pair too), and
+ *   the target coordinates are given on the forward target, t_start = L - 1 - t_end',
+ *   t_end = L - 1 - t_start' (L the target's length), so t_start <= t_end; an empty pair keeps 0.
+ * Its CIGAR runs forward along the query and from t_end down to t_start along the complemented
+ * target.  A slot that names no pair is never a reverse hit.  sw_last_kernel reports
+ * "align-strand i32 nq=<nq> hits=<n_hits> chunks=<c>". */
+enum { SW_ALIGN_REVERSE = 8 }; /* flag: aligned against the reverse complement of the target */
+
+sw_status sw_align_strand_hits_device(sw_bank *bank, const uint8_t *d_residues,
+                                      const uint64_t *d_offsets, const uint32_t *d_lens,
+                                      const uint64_t *d_ids, size_t n, uint32_t max_len,
+                                      const uint8_t *d_strands, const uint32_t *d_hit_queries,
+                                      size_t hits_per_query, const uint64_t *d_hits,
+                                      size_t n_hits, sw_alignment *d_out, uint32_t *d_cigar,
+                                      uint32_t cigar_stride, void *stream);
+
+sw_status sw_align_strand_hits(sw_bank *bank, const uint8_t *residues, size_t residues_len,
+                               const uint64_t *offsets, const uint32_t *lens, const uint64_t *ids,
+                               size_t n, const uint8_t *strands, const uint32_t *hit_queries,
+                               size_t hits_per_query, const uint64_t *hits, size_t n_hits,
+                               sw_alignment *out, uint32_t *cigar, size_t cigar_cap,
+                               size_t *cigar_used);
 
 /* ---- profiling (≙ the CAPI AFU's cycle counters, capi_sample_aligner/hdl-verliog/afu.v
  *      _DEBUGGING_ "calculation #N completed, runtime: C cycles") ------------------------- */

@@ -39,6 +39,11 @@ typedef struct SwkAlign {
   uint32_t nq;
   const uint32_t* hit_queries; /* or NULL: hits_per_query >= 1 */
   uint32_t hits_per_query;
+  /* the strand call (set != 0): hit h (query i, target t) is aligned against the reverse
+   * complement of its target when strands[i * n + t], or strands[h] with strand_by_hit, is not 0;
+   * NULL: every hit is on the forward strand and the set kernels run */
+  const uint8_t* strands;
+  int strand_by_hit;
 } SwkAlign;
 
 /* Where one hit's window sits in the direction store (dwords) and its ops in the CIGAR buffer. */
@@ -57,6 +62,8 @@ hipError_t swk_launch_align_ends(const SwkAlign* p, hipStream_t st);
 hipError_t swk_launch_align_paths(const SwkAlign* p, const uint32_t* list, size_t h0, size_t count,
                                   const SwkAlignPlan* plan, uint64_t slot, uint32_t* dirs,
                                   hipStream_t st);
+/* After the paths of a strand call: SW_ALIGN_REVERSE and forward target coordinates. */
+hipError_t swk_launch_align_flip(const SwkAlign* p, hipStream_t st);
 #ifdef __cplusplus
 }
 #endif

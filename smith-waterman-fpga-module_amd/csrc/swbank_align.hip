@@ -1,7 +1,8 @@
 // swbank_align.hip — alignments of chosen hits (include/swbank.h "alignments of chosen hits",
 // DESIGN.md §3.9): the ABI entries for one query (sw_align_hits*) and for a query set
-// (sw_align_set_hits*), the chunking of the direction store, the host calls' staging.  Both pairs
-// of entries run the same code; they differ in the pair list.  The kernels are in
+// (sw_align_set_hits*), and for a set with a strand per pair (sw_align_strand_hits*, DESIGN.md
+// §3.13), the chunking of the direction store, the host calls' staging.  All entries run the same
+// code; they differ in the pair list.  The kernels are in
 // swbank_kalign.hip.
 #include "swbank_bank.h"
 
@@ -21,6 +22,9 @@ struct Pairs {
   size_t hits_per_query;
   const uint64_t* hits;
   size_t n_hits;
+  // sw_align_strand_hits*: the nq x n strand matrix (NULL: every hit on the forward strand)
+  bool strand_call = false;
+  const uint8_t* strands = nullptr;
 };
 
 size_t query_count(const sw_bank* b) { return b->qset.size() > 1 ? b->qset.size() : 1; }
@@ -128,8 +132,11 @@ sw_status paths_by_slot(sw_bank* b, const SwkAlign& p, uint32_t max_len, hipStre
   return SW_OK;
 }
 
-void name_kernel(sw_bank* b, bool set, size_t hits, size_t chunks) {
-  if (set)
+void name_kernel(sw_bank* b, bool set, size_t hits, size_t chunks, bool strand = false) {
+  if (strand)
+    snprintf(b->last_kernel, sizeof(b->last_kernel), "align-strand i32 nq=%zu hits=%zu chunks=%zu",
+             query_count(b), hits, chunks);
+  else if (set)
     snprintf(b->last_kernel, sizeof(b->last_kernel), "align-set i32 nq=%zu hits=%zu chunks=%zu",
              query_count(b), hits, chunks);
   else
@@ -150,6 +157,7 @@ sw_status device_launch(sw_bank* b, const uint8_t* d_res, const uint64_t* d_offs
   p.n = n;
   p.hit_queries = pr.hit_queries;
   p.hits_per_query = (uint32_t)pr.hits_per_query;
+  p.strands = pr.strands;
   p.out = d_out;
   p.cigar = d_cigar;
   p.cigar_stride = d_cigar ? stride : 0;
@@ -168,8 +176,9 @@ sw_status device_launch(sw_bank* b, const uint8_t* d_res, const uint64_t* d_offs
     if ((st = paths_by_slot(b, p, max_len, hs, chunks)) != SW_OK) return st;
     if ((st = cd.end()) != SW_OK) return st;
   }
+  HIPOK(b, swk_launch_align_flip(&p, hs));  // (a strand call: after the last pass)
   HIPOK(b, hipEventRecord(b->ev_used, hs));
-  name_kernel(b, pr.set, pr.n_hits, chunks);
+  name_kernel(b, pr.set, pr.n_hits, chunks, pr.strand_call);
   return SW_OK;
 }
 
@@ -180,6 +189,8 @@ sw_status device_call(sw_bank* b, const uint8_t* d_res, const uint64_t* d_offs,
                       uint32_t cigar_stride, void* stream) {
   DevGuard dev_guard(b);  // on the bank's device; the caller's is restored on return (ABI 6)
   if (!b) return SW_ERR_ARG;
+  if (pr.strand_call && b->cfg.alphabet != SW_ALPHABET_DNA)
+    return fail(b, SW_ERR_UNSUPPORTED, "strand alignments: DNA banks only");
   if (b->is_multi()) {  // on the root device, where the caller's buffers are
     sw_bank* k = b->kids[0];
     if (!b->have_query) return fail(b, SW_ERR_STATE, "penalties or query not loaded");
@@ -215,6 +226,8 @@ sw_status host_call(sw_bank* b, const uint8_t* residues, size_t residues_len,
   DevGuard dev_guard(b);  // on the bank's device; the caller's is restored on return (ABI 6)
   if (!b) return SW_ERR_ARG;
   if (cigar_used) *cigar_used = 0;
+  if (pr.strand_call && b->cfg.alphabet != SW_ALPHABET_DNA)
+    return fail(b, SW_ERR_UNSUPPORTED, "strand alignments: DNA banks only");
   if (b->is_multi()) {  // on the root device: hit lists are small
     sw_bank* k = b->kids[0];
     if (!b->have_query) return fail(b, SW_ERR_STATE, "penalties or query not loaded");
@@ -239,6 +252,7 @@ sw_status host_call(sw_bank* b, const uint8_t* residues, size_t residues_len,
   const auto target_of = [&](size_t h) { return pr.hits ? pr.hits[h] : (uint64_t)h; };
   std::vector<uint64_t> goffs(n_hits);
   std::vector<uint32_t> glens(n_hits), gq(pr.set ? n_hits : 0);
+  std::vector<uint8_t> gs(pr.strands ? n_hits : 0);  // a strand call: each hit's strand
   uint64_t total = 0;
   uint32_t max_len = 0;
   for (size_t h = 0; h < n_hits; ++h) {
@@ -259,6 +273,7 @@ sw_status host_call(sw_bank* b, const uint8_t* residues, size_t residues_len,
     if (l && (!residues || o > residues_len || l > residues_len - o))
       return fail(b, SW_ERR_ARG, "target %llu outside the residues", (unsigned long long)t);
     glens[h] = (uint32_t)l;
+    if (pr.strands) gs[h] = pr.strands[(size_t)gq[h] * n + t] != 0;
     total += l;
     max_len = std::max(max_len, (uint32_t)l);
   }
@@ -279,6 +294,7 @@ sw_status host_call(sw_bank* b, const uint8_t* residues, size_t residues_len,
   HIPOK(b, b->al_lens.reserve(n_hits));
   HIPOK(b, b->al_out.reserve(n_hits));
   if (pr.set) HIPOK(b, b->al_hq.reserve(n_hits));
+  if (pr.strands) HIPOK(b, b->al_hs.reserve(n_hits));
   HIPOK(b, hipStreamWaitEvent(hs, b->ev_ready, 0));
   HIPOK(b, hipStreamWaitEvent(hs, b->ev_used, 0));  // an earlier call may still read the buffers
   HIPOK(b, hipMemcpyAsync(b->al_res.p, gres.data(), gres.size(), hipMemcpyHostToDevice, hs));
@@ -286,6 +302,8 @@ sw_status host_call(sw_bank* b, const uint8_t* residues, size_t residues_len,
   HIPOK(b, hipMemcpyAsync(b->al_lens.p, glens.data(), n_hits * 4, hipMemcpyHostToDevice, hs));
   if (pr.set)
     HIPOK(b, hipMemcpyAsync(b->al_hq.p, gq.data(), n_hits * 4, hipMemcpyHostToDevice, hs));
+  if (pr.strands)
+    HIPOK(b, hipMemcpyAsync(b->al_hs.p, gs.data(), n_hits, hipMemcpyHostToDevice, hs));
   __atomic_fetch_add(&b->ctr.h2d_bytes, gres.size() + n_hits * (pr.set ? 16 : 12),
                      __ATOMIC_RELAXED);
   SwkAlign p{};
@@ -297,6 +315,10 @@ sw_status host_call(sw_bank* b, const uint8_t* residues, size_t residues_len,
     p.set = 1;
     p.n = n_hits;
     p.hit_queries = b->al_hq.p;
+  }
+  if (pr.strands) {  // ... on strand al_hs[h]
+    p.strands = b->al_hs.p;
+    p.strand_by_hit = 1;
   }
   if ((st = align_block(b, p, n_hits, max_len)) != SW_OK) return st;
   Timed ab{b, hs};
@@ -387,8 +409,16 @@ sw_status host_call(sw_bank* b, const uint8_t* residues, size_t residues_len,
     const uint64_t t = target_of(h);
     out[h].index = t;
     out[h].id = ids ? ids[t] : t;
+    if (pr.strands && gs[h]) {  // the reverse strand: coordinates on the forward target
+      out[h].flags |= SW_ALIGN_REVERSE;
+      if (out[h].score > 0) {
+        const uint32_t ts = out[h].t_start, te = out[h].t_end;
+        out[h].t_start = glens[h] - 1 - te;
+        out[h].t_end = glens[h] - 1 - ts;
+      }
+    }
   }
-  name_kernel(b, pr.set, n_hits, chunks);
+  name_kernel(b, pr.set, n_hits, chunks, pr.strand_call);
   return SW_OK;
 }
 
@@ -436,4 +466,29 @@ extern "C" sw_status sw_align_set_hits(sw_bank* b, const uint8_t* residues, size
   return host_call(b, residues, residues_len, offsets, lens, ids, n,
                    Pairs{true, hit_queries, hits_per_query, hits, n_hits}, out, cigar, cigar_cap,
                    cigar_used);
+}
+
+extern "C" sw_status sw_align_strand_hits_device(sw_bank* b, const uint8_t* d_res,
+                                                 const uint64_t* d_offs, const uint32_t* d_lens,
+                                                 const uint64_t* d_ids, size_t n, uint32_t max_len,
+                                                 const uint8_t* d_strands,
+                                                 const uint32_t* d_hit_queries,
+                                                 size_t hits_per_query, const uint64_t* d_hits,
+                                                 size_t n_hits, sw_alignment* d_out,
+                                                 uint32_t* d_cigar, uint32_t cigar_stride,
+                                                 void* stream) {
+  return device_call(b, d_res, d_offs, d_lens, d_ids, n, max_len,
+                     Pairs{true, d_hit_queries, hits_per_query, d_hits, n_hits, true, d_strands},
+                     d_out, d_cigar, cigar_stride, stream);
+}
+
+extern "C" sw_status sw_align_strand_hits(sw_bank* b, const uint8_t* residues, size_t residues_len,
+                                          const uint64_t* offsets, const uint32_t* lens,
+                                          const uint64_t* ids, size_t n, const uint8_t* strands,
+                                          const uint32_t* hit_queries, size_t hits_per_query,
+                                          const uint64_t* hits, size_t n_hits, sw_alignment* out,
+                                          uint32_t* cigar, size_t cigar_cap, size_t* cigar_used) {
+  return host_call(b, residues, residues_len, offsets, lens, ids, n,
+                   Pairs{true, hit_queries, hits_per_query, hits, n_hits, true, strands}, out,
+                   cigar, cigar_cap, cigar_used);
 }

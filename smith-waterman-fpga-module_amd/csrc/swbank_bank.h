@@ -6,7 +6,8 @@
 // per call), swbank_multi.hip (multi-device banks and the RCCL gather), swbank_align.hip
 // (alignments of chosen hits, of one query or a query set), swbank_top.hip (the k best hits of
 // every row of a score matrix, the best query of every column), swbank_stat.hip (hit
-// statistics: the seeded shuffle, the score histogram, the estimate, bits and E-values).
+// statistics: the seeded shuffle, the score histogram, the estimate, bits and E-values),
+// swbank_strand.hip (both DNA strands: the reverse complement, the strand-merged scores).
 #ifndef SWBANK_BANK_H
 #define SWBANK_BANK_H
 
@@ -124,6 +125,15 @@ extern "C" hipError_t swk_stat_hist(const int32_t* scores, const uint32_t* lens,
                                     unsigned long long* len_sums, unsigned long long* clamped,
                                     hipStream_t st);
 extern "C" size_t swk_stat_par_doubles(void);
+// swbank_kstrand.hip: the reverse complement of a batch (stride == 0: into the caller's layout;
+// else at a fixed stride, the offsets written to out_offs) and the strand merge of two score
+// matrices: fwd[i * n + k] = max(fwd, rev[i * nk + k - k0]) over k in [k0, k0 + nk), strands
+// (optional) 1 where the reverse score is strictly greater
+extern "C" hipError_t swk_revcomp_batch(const uint8_t* in, const uint64_t* offs,
+                                        const uint32_t* lens, size_t n, uint8_t* out,
+                                        uint64_t* out_offs, uint32_t stride, hipStream_t st);
+extern "C" hipError_t swk_strand_merge(int32_t* fwd, const int32_t* rev, uint8_t* strands, size_t n,
+                                       size_t k0, size_t nk, size_t nq, hipStream_t st);
 extern "C" hipError_t swk_stat_signif(const double* par, const int32_t* hit_scores,
                                       const uint64_t* hits, const uint32_t* lens, size_t k,
                                       size_t nq, double db_size, double* bits, double* evalues,
@@ -447,9 +457,9 @@ struct sw_bank {
   // device (al_tab: an {offset, length} entry per query, alpha x alpha scores, then the codes of
   // the query or of every query of the set; built on first use per query or set), per-wave
   // scratch rows, the direction store; the host-buffer call's gathered targets, records, ops,
-  // window plan and chunk lists, and (a set call) each hit's query
+  // window plan and chunk lists, (a set call) each hit's query and (a strand call) its strand
   bool al_ready = false;
-  DevBuf<uint8_t> al_tab, al_res;
+  DevBuf<uint8_t> al_tab, al_res, al_hs;
   DevBuf<uint2> al_scr;
   DevBuf<uint32_t> al_dirs, al_lens, al_cig, al_list, al_hq;
   DevBuf<uint64_t> al_offs;
@@ -477,6 +487,15 @@ struct sw_bank {
   DevBuf<double> stat_par;
   std::vector<double> stat_hpar;  // (the upload's source, kept until ev_stat)
   hipEvent_t ev_stat = nullptr;
+  // both strands (swbank_strand.hip): the reverse complement of a slice of targets at a fixed
+  // stride, its offsets, the slice's reverse-strand scores; the host forms' batch, merged scores
+  // and strands on the device; ev_strand follows the last call's use of them, on whichever
+  // stream it ran, and the next call's stream waits for it
+  DevBuf<uint8_t> str_codes, str_hres, str_hstr;
+  DevBuf<uint64_t> str_offs, str_hoffs;
+  DevBuf<uint32_t> str_hlens;
+  DevBuf<int32_t> str_scores, str_hsc;
+  hipEvent_t ev_strand = nullptr;
   struct Seg { int W; size_t off, off16; };  // rows = W*R (last may be shorter); word offsets
                                               // in qtab and qtab16
   std::vector<Seg> segs;

@@ -178,6 +178,7 @@ extern "C" void sw_bank_destroy(sw_bank* b) {
   if (b->stream) (void)hipStreamSynchronize(b->stream);
   if (b->ev_top) (void)hipEventSynchronize(b->ev_top);  // the last top-hits call, on any stream
   if (b->ev_stat) (void)hipEventSynchronize(b->ev_stat);  // ... significance call
+  if (b->ev_strand) (void)hipEventSynchronize(b->ev_strand);  // ... strand call
   uint64_t nl;
   double pm, sm;
   (void)sw_bank_timing(b, &nl, &pm, &sm);
@@ -196,6 +197,7 @@ extern "C" void sw_bank_destroy(sw_bank* b) {
   if (b->best_ev) (void)hipEventDestroy(b->best_ev);
   if (b->ev_top) (void)hipEventDestroy(b->ev_top);
   if (b->ev_stat) (void)hipEventDestroy(b->ev_stat);
+  if (b->ev_strand) (void)hipEventDestroy(b->ev_strand);
   if (b->ev_join) (void)hipEventDestroy(b->ev_join);
   for (hipEvent_t e : b->deal_ev) (void)hipEventDestroy(e);
   b->fb_idx.release();
@@ -212,6 +214,7 @@ extern "C" void sw_bank_destroy(sw_bank* b) {
   b->al_cig.release();
   b->al_list.release();
   b->al_hq.release();
+  b->al_hs.release();
   b->al_offs.release();
   b->al_out.release();
   b->al_plan.release();
@@ -229,6 +232,14 @@ extern "C" void sw_bank_destroy(sw_bank* b) {
   b->stat_scores.release();
   b->stat_cnt.release();
   b->stat_par.release();
+  b->str_codes.release();
+  b->str_hres.release();
+  b->str_hstr.release();
+  b->str_offs.release();
+  b->str_hoffs.release();
+  b->str_hlens.release();
+  b->str_scores.release();
+  b->str_hsc.release();
   b->dperm.release();
   b->dsort.release();
   b->bal_state.release();
@@ -367,6 +378,7 @@ extern "C" sw_status sw_bank_sync(sw_bank* b) {
   if (e == hipSuccess && b->ev_used) e = hipEventSynchronize(b->ev_used);
   if (e == hipSuccess && b->ev_top) e = hipEventSynchronize(b->ev_top);  // ... of a top-hits call
   if (e == hipSuccess && b->ev_stat) e = hipEventSynchronize(b->ev_stat);  // ... significance
+  if (e == hipSuccess && b->ev_strand) e = hipEventSynchronize(b->ev_strand);  // ... strands
   if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
   (void)hipSetDevice(cur);
   HIPOK(b, e);

@@ -9,7 +9,7 @@
  *
  * Usage: swbank -q query.fa -l library.fa [-p match,mismatch,open,extend] [-P] [-g]
  *               [-d device[,device...]] [-o out.txt] [-T] [-R scores.txt] [-b] [-A k]
- *               [-E rounds[,seed]] [-S lambda,K]
+ *               [-E rounds[,seed]] [-S lambda,K] [-B]
  *   -p  penalties (default 5,-4,-12,-4: ScoreBank_v1_tb.sv:16-19, data/smith-waterman.py:6-10)
  *   -P  protein mode (BLOSUM62; -p gives only open,extend)      -g  Gotoh gap model
  *   -T  testbench transcript format "@     0ns: %10s score: \t%d"
@@ -30,6 +30,16 @@
  *       Either prints "Statistics: Lambda= L;  K=K (n samples)" after the score lines and extends
  *       every hit's " s-w opt: S" line of -A to " s-w opt: S  bits: B E(n): E" with n = the
  *       library's record count (data/alignments500.txt:24); without them nothing changes
+ *   -B  search both DNA strands (sw_score_strands; what ssearch36 does without its -3 switch,
+ *       which the reference's runs set, data/alignments500.txt:1): every score is the better of
+ *       the forward score and the score against the record's reverse complement, and " [f]" or
+ *       " [r]" (the reverse score strictly greater) follows it on every score line.  -A aligns
+ *       each hit on its strand (sw_align_strand_hits), prints the strand after ">>name (len nt)"
+ *       and, for [r], the overlap's target range high to low on the forward record: the
+ *       alignment runs down it.  With -E / -S the E-values take db_size = 2 x the record count
+ *       (two strands are a library twice the size; the reference, run with -3, pins no such
+ *       convention), printed as E(2n); -E still fits lambda and K on forward shuffles.  The -R
+ *       file keeps its layout (scores only).  Not with -P.
  *   -b  also print the bank's best hit ("best: >name score: S", ≙ max / vld_max) to stderr
  * FASTA: '>' starts a record (name = first token); sequence lines are concatenated; CR/LF,
  * blank lines and lower case are accepted; bytes outside the alphabet encode to N (DNA) or X
@@ -118,7 +128,7 @@ static void usage(const char *argv0) {
   fprintf(stderr,
           "usage: %s -q query.fa -l library.fa [-p match,mismatch,open,extend] [-P] [-g]\n"
           "          [-d device[,device...]] [-o out.txt] [-T] [-R scores.txt] [-b] [-A k]\n"
-          "          [-E rounds[,seed]] [-S lambda,K]\n",
+          "          [-E rounds[,seed]] [-S lambda,K] [-B]\n",
           argv0);
 }
 
@@ -134,7 +144,7 @@ static int by_score(const void *a, const void *b) {
 static int print_alignments(FILE *out, sw_bank *bank, const uint8_t *res, size_t total,
                             const uint64_t *offs, const uint32_t *lens, const int32_t *scores,
                             const fasta_t *lib, size_t asked, const char *unit,
-                            const sw_statistics *stats) {
+                            const sw_statistics *stats, const uint8_t *strands) {
   const size_t k = asked < lib->n ? asked : lib->n;
   const int on_device = asked <= SW_TOP_MAX_K; /* (what -A asked for picks the path) */
   uint64_t *order = malloc((on_device ? k : lib->n) * sizeof(uint64_t));
@@ -157,30 +167,39 @@ static int print_alignments(FILE *out, sw_bank *bank, const uint8_t *res, size_t
   if (st == SW_OK) {
     for (size_t i = 0; i < k; ++i) cap += 2 * (size_t)lens[order[i]]; /* ops a path can have */
     cig = malloc(cap * sizeof(uint32_t));
-    st = cig ? sw_align_hits(bank, res, total, offs, lens, NULL, lib->n, order, k, al, cig, cap,
-                             &used)
-             : SW_ERR_NOMEM;
+    if (!cig)
+      st = SW_ERR_NOMEM;
+    else if (strands) /* -B: one query, the [1, k] layout */
+      st = sw_align_strand_hits(bank, res, total, offs, lens, NULL, lib->n, strands, NULL, k, order,
+                                k, al, cig, cap, &used);
+    else
+      st = sw_align_hits(bank, res, total, offs, lens, NULL, lib->n, order, k, al, cig, cap, &used);
   }
   if (st != SW_OK) {
     fprintf(stderr, "swbank: %s: %s\n", sw_status_string(st), sw_last_error(bank));
   } else {
     for (size_t i = 0; i < k; ++i) {
       const sw_alignment *a = &al[i];
-      fprintf(out, ">>%s (%u %s)\n s-w opt: %d", lib->names[a->index], lens[a->index], unit,
-              a->score);
+      const int rev = (a->flags & SW_ALIGN_REVERSE) != 0;
+      const size_t db = strands ? 2 * lib->n : lib->n; /* two strands: twice the library */
+      fprintf(out, ">>%s (%u %s)%s\n s-w opt: %d", lib->names[a->index], lens[a->index], unit,
+              strands ? (rev ? " [r]" : " [f]") : "", a->score);
       double bits, ev;
-      if (stats && sw_hit_significance(stats, &a->score, &lens[a->index], 1, lib->n, &bits, &ev) ==
+      if (stats && sw_hit_significance(stats, &a->score, &lens[a->index], 1, db, &bits, &ev) ==
                        SW_OK)
-        fprintf(out, "  bits: %.1f E(%zu): %.2g", bits, lib->n, ev);
+        fprintf(out, "  bits: %.1f E(%zu): %.2g", bits, db, ev);
       fputc('\n', out);
       if (a->flags & SW_ALIGN_EMPTY) continue;
-      if (a->flags == 0) {
+      /* the target range of a reverse hit runs high to low on the forward record */
+      const uint32_t t_from = rev ? a->t_end + 1 : a->t_start + 1;
+      const uint32_t t_to = rev ? a->t_start + 1 : a->t_end + 1;
+      if ((a->flags & ~(uint32_t)SW_ALIGN_REVERSE) == 0) {
         const double pct = 100.0 * a->n_identities / a->n_columns;
         fprintf(out,
                 "Smith-Waterman score: %d; %.1f%% identity (%.1f%% similar) in %u %s overlap "
                 "(%u-%u:%u-%u)\n",
-                a->score, pct, pct, a->n_columns, unit, a->q_start + 1, a->q_end + 1,
-                a->t_start + 1, a->t_end + 1);
+                a->score, pct, pct, a->n_columns, unit, a->q_start + 1, a->q_end + 1, t_from,
+                t_to);
         const size_t need = sw_cigar_string(cig + a->cigar_offset, a->cigar_len, NULL, 0);
         char *text = malloc(need + 1);
         if (text) {
@@ -190,7 +209,7 @@ static int print_alignments(FILE *out, sw_bank *bank, const uint8_t *res, size_t
         }
       } else { /* coordinates without a path (a window past SWBANK_ALIGN_MB) */
         fprintf(out, "Smith-Waterman score: %d; no path (%u-%u:%u-%u)\ncigar: *\n", a->score,
-                a->q_start + 1, a->q_end + 1, a->t_start + 1, a->t_end + 1);
+                a->q_start + 1, a->q_end + 1, t_from, t_to);
       }
     }
   }
@@ -202,7 +221,7 @@ static int print_alignments(FILE *out, sw_bank *bank, const uint8_t *res, size_t
 
 int main(int argc, char **argv) {
   const char *qpath = NULL, *lpath = NULL, *opath = NULL, *pen = NULL, *rpath = NULL;
-  int protein = 0, gotoh = 0, device = -1, transcript = 0, best = 0, opt;
+  int protein = 0, gotoh = 0, device = -1, transcript = 0, best = 0, both = 0, opt;
   int ndev = 0, devs[SW_MAX_DEVICES];
   long nalign = 0;
   int have_stats = 0; /* 1: -S (given), 2: -E (estimated) */
@@ -210,7 +229,7 @@ int main(int argc, char **argv) {
   unsigned long long stat_seed = 0;
   sw_statistics stats;
   memset(&stats, 0, sizeof(stats));
-  while ((opt = getopt(argc, argv, "q:l:p:Pgd:o:TR:bA:E:S:h")) != -1) {
+  while ((opt = getopt(argc, argv, "q:l:p:Pgd:o:TR:bA:E:S:Bh")) != -1) {
     switch (opt) {
       case 'q': qpath = optarg; break;
       case 'l': lpath = optarg; break;
@@ -231,6 +250,7 @@ int main(int argc, char **argv) {
         break;
       }
       case 'b': best = 1; break;
+      case 'B': both = 1; break;
       case 'A': {
         char *end;
         nalign = strtol(optarg, &end, 10);
@@ -264,6 +284,11 @@ int main(int argc, char **argv) {
   }
   if (!qpath || !lpath) {
     fprintf(stderr, "Input files missing\n");
+    usage(argv[0]);
+    return 1;
+  }
+  if (both && protein) {
+    fprintf(stderr, "-B searches DNA strands: not with -P\n");
     usage(argv[0]);
     return 1;
   }
@@ -321,7 +346,8 @@ int main(int argc, char **argv) {
   uint64_t *offs = malloc((lib.n + 1) * sizeof(uint64_t));
   uint32_t *lens = malloc((lib.n + 1) * sizeof(uint32_t));
   int32_t *scores = malloc((lib.n + 1) * sizeof(int32_t));
-  if (!res || !offs || !lens || !scores) st = SW_ERR_NOMEM;
+  uint8_t *strands = both ? calloc(lib.n + 1, 1) : NULL;
+  if (!res || !offs || !lens || !scores || (both && !strands)) st = SW_ERR_NOMEM;
   size_t pos = 0;
   for (size_t k = 0; st == SW_OK && k < lib.n; ++k) {
     size_t l = strlen(lib.seqs[k]);
@@ -330,7 +356,9 @@ int main(int argc, char **argv) {
     lens[k] = (uint32_t)l;
     pos += l;
   }
-  if (st == SW_OK) st = sw_score_batch(bank, res, total, offs, lens, NULL, lib.n, scores);
+  if (st == SW_OK)
+    st = both ? sw_score_strands(bank, res, total, offs, lens, lib.n, scores, strands)
+              : sw_score_batch(bank, res, total, offs, lens, NULL, lib.n, scores);
   if (st == SW_OK && have_stats == 2 && lib.n)
     st = sw_estimate_statistics(bank, res, total, offs, lens, lib.n, stat_seed,
                                 (uint32_t)stat_rounds, &stats);
@@ -348,17 +376,18 @@ int main(int argc, char **argv) {
   for (size_t k = 0; k < lib.n; ++k) {
     char nm[256];
     snprintf(nm, sizeof(nm), ">%s", lib.names[k]);
+    const char *sd = both ? (strands[k] ? " [r]" : " [f]") : "";
     if (transcript)
-      fprintf(out, "@%6dns: %10s score: \t%10d\n", 0, nm, scores[k]);
+      fprintf(out, "@%6dns: %10s score: \t%10d%s\n", 0, nm, scores[k], sd);
     else
-      fprintf(out, "%s score: %d\n", nm, scores[k]);
+      fprintf(out, "%s score: %d%s\n", nm, scores[k], sd);
   }
   if (have_stats)
     fprintf(out, "Statistics: Lambda= %.4f;  K=%.4f (%llu samples)\n", stats.lambda, stats.K,
             (unsigned long long)stats.n_samples);
   if (nalign > 0 && lib.n) {
     int rc = print_alignments(out, bank, res, total, offs, lens, scores, &lib, (size_t)nalign,
-                              protein ? "aa" : "nt", have_stats ? &stats : NULL);
+                              protein ? "aa" : "nt", have_stats ? &stats : NULL, strands);
     if (rc) {
       if (opath) fclose(out);
       sw_bank_destroy(bank);
@@ -368,8 +397,12 @@ int main(int argc, char **argv) {
   if (opath) fclose(out);
   uint64_t bid = 0;
   int32_t bsc = 0;
-  if (best && lib.n && sw_batch_best(bank, &bid, &bsc, NULL) == SW_OK)
-    fprintf(stderr, "best: >%s score: %d\n", lib.names[bid], bsc);
+  /* (-B tracks no best hit on the device: the lowest index with the best merged score) */
+  if (best && lib.n &&
+      (both ? sw_best_hit(bank, scores, NULL, lib.n, &bid, &bsc)
+            : sw_batch_best(bank, &bid, &bsc, NULL)) == SW_OK)
+    fprintf(stderr, "best: >%s score: %d%s\n", lib.names[bid], bsc,
+            both ? (strands[bid] ? " [r]" : " [f]") : "");
   if (rpath) { /* ssearch36 -R layout (data/score500.txt:1-3,502-503) */
     FILE *rf = fopen(rpath, "w");
     if (!rf) {
@@ -398,5 +431,6 @@ int main(int argc, char **argv) {
   free(offs);
   free(lens);
   free(scores);
+  free(strands);
   return 0;
 }

@@ -88,6 +88,18 @@ size_t sw_unpack_2bit(const uint8_t *packed, size_t n, uint8_t *codes) {
   return n;
 }
 
+/* T <-> A (0 <-> 2), C <-> G (1 <-> 3); N and anything past it stays.  out may be codes. */
+size_t sw_revcomp_codes(const uint8_t *codes, size_t n, uint8_t *out) {
+  if (!codes || !out) return 0;
+  for (size_t i = 0, j = n; i < j; ++i) {
+    --j;
+    const uint8_t a = codes[i], b = codes[j];
+    out[i] = (uint8_t)(b < 4 ? b ^ 2 : b);
+    out[j] = (uint8_t)(a < 4 ? a ^ 2 : a);
+  }
+  return n;
+}
+
 /* BLOSUM62 in NCBI order ARNDCQEGHILKMFPSTWYVBZX*. */
 static const int8_t kBlosum62[SW_PROTEIN_ALPHA][SW_PROTEIN_ALPHA] = {
     {4, -1, -2, -2, 0, -1, -1, 0, -2, -1, -1, -1, -1, -2, -1, 1, 0, -3, -2, 0, -2, -1, 0, -4},

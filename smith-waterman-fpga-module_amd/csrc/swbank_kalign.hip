@@ -20,7 +20,12 @@
 //
 // The kernels are templated on SET: the SET instances serve sw_align_set_hits* and take each
 // hit's query from a table of the loaded set (al_query); the others are the single-query
-// kernels, which the set costs nothing.
+// kernels, which the set costs nothing.  STRAND (with SET; sw_align_strand_hits*): a hit whose
+// strand is 1 is aligned against the reverse complement of its target without a copy of it: the
+// walks read the target from its far end with the opposite step (AlSeq.tstep) under a
+// column-complemented copy of the matrix, so the profile build and al_walk are what they are;
+// the records keep the coordinates of the reverse-complemented target until align_flip, after
+// the last pass that reads them.
 #include "swbank.h"
 #include "swbank_align.h"
 #include "swbank_kcommon.h"
@@ -65,6 +70,10 @@ struct AlignArgs {
   const uint32_t* hit_queries;
   uint32_t nq, hits_per_query;
   size_t n;
+  // the STRAND kernels: hit h (query i, target t) is on the reverse strand when strands[h]
+  // (strand_by_hit: the host call's gathered list) or strands[i * n + t] is not 0
+  const uint8_t* strands;
+  uint32_t strand_by_hit;
 };
 
 // Hit h's query.  !SET: the one loaded query.  SET: the hit's own; len = 0xFFFFFFFF when the hit
@@ -88,6 +97,14 @@ __device__ __forceinline__ AlQuery al_query(const AlignArgs& a, size_t h) {
   }
   return AlQuery{a.query + e.x, e.y};
 }
+
+// Whether hit h (target t) lies on the reverse strand; the hit names a pair.
+__device__ __forceinline__ bool al_reverse(const AlignArgs& a, size_t h, uint64_t t) {
+  if (a.strand_by_hit) return a.strands[h] != 0;
+  const uint32_t qi = a.hit_queries ? a.hit_queries[h] : (uint32_t)h / a.hits_per_query;
+  return a.strands[(size_t)qi * a.n + t] != 0;
+}
+__device__ __forceinline__ uint32_t al_comp(uint32_t c) { return c < 4 ? c ^ 2u : c; }
 
 __device__ __forceinline__ int32_t al_lane0(int32_t inj, int32_t v) {  // wave_shr:1
   return __builtin_amdgcn_update_dpp(inj, v, 0x138, 0xF, 0xF, false);
@@ -249,16 +266,28 @@ __device__ __forceinline__ void al_load_matrix(const AlignArgs& a, int8_t* smat)
   for (uint32_t i = threadIdx.x; i < a.alpha * a.alpha; i += blockDim.x) smat[i] = a.mat[i];
   __syncthreads();
 }
+// The matrix and its column complement: smat[1][q * A + c] scores q against the complement of c.
+__device__ __forceinline__ void al_load_matrices(const AlignArgs& a,
+                                                 int8_t (&smat)[2][AL_LETTERS * AL_LETTERS]) {
+  for (uint32_t i = threadIdx.x; i < a.alpha * a.alpha; i += blockDim.x) {
+    const uint32_t q = i / a.alpha, c = i % a.alpha, cc = al_comp(c);
+    smat[0][i] = a.mat[i];
+    smat[1][i] = a.mat[q * a.alpha + (cc < a.alpha ? cc : c)];
+  }
+  __syncthreads();
+}
 
 // Passes A and B: score and end cell (forward), start cell (the same walk over the reversed
 // prefixes q[q_end..0] x t[t_end..0]); writes the hit's whole record, without a path.
 // SET: the hit's own query of a set; a hit that names no pair gets its record here (index = id =
 // SW_HIT_NONE, SW_ALIGN_EMPTY | SW_ALIGN_NO_HIT) and nothing of the batch is read for it.
-template <bool GOTOH, bool SET>
+template <bool GOTOH, bool SET, bool STRAND = false>
 __global__ void __launch_bounds__(256) align_ends(const AlignArgs a) {
+  static_assert(SET || !STRAND, "the strand kernels are set kernels");
   __shared__ uint2 lp[4][AL_LETTERS][64];
-  __shared__ int8_t smat[AL_LETTERS * AL_LETTERS];
-  al_load_matrix(a, smat);
+  __shared__ int8_t smats[STRAND ? 2 : 1][AL_LETTERS * AL_LETTERS];
+  if constexpr (STRAND) al_load_matrices(a, smats);
+  else al_load_matrix(a, smats[0]);
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const size_t gw = (size_t)blockIdx.x * 4 + wave, GW = (size_t)gridDim.x * 4;
@@ -284,10 +313,19 @@ __global__ void __launch_bounds__(256) align_ends(const AlignArgs a) {
     }
     uint32_t L = a.lens[t];
     const uint8_t* tp = a.res + (L ? a.offs[t] : 0);
+    int32_t td = 1;  // the step along the target: -1 from its far end on the reverse strand
+    const int8_t* smat = smats[0];
+    if constexpr (STRAND) {
+      if (L && __builtin_amdgcn_readfirstlane((int)al_reverse(a, h, t))) {
+        tp += L - 1;
+        td = -1;
+        smat = smats[1];
+      }
+    }
     L = __builtin_amdgcn_readfirstlane(min(L, a.scols));
     int32_t score, rs;
     uint32_t qe, te, ri, rj;
-    al_walk<GOTOH, false>(a, smat, lp[wave], scr, AlSeq{qy.p, tp, 1, 1, qy.len, L}, nullptr,
+    al_walk<GOTOH, false>(a, smat, lp[wave], scr, AlSeq{qy.p, tp, 1, td, qy.len, L}, nullptr,
                           score, qe, te);
     score = __builtin_amdgcn_readfirstlane(score);
     qe = __builtin_amdgcn_readfirstlane(qe);
@@ -295,8 +333,8 @@ __global__ void __launch_bounds__(256) align_ends(const AlignArgs a) {
     uint32_t qs = 0, ts = 0;
     if (score > 0) {
       al_walk<GOTOH, false>(a, smat, lp[wave], scr,
-                            AlSeq{qy.p + qe, tp + te, -1, -1, qe + 1, te + 1}, nullptr, rs, ri,
-                            rj);
+                            AlSeq{qy.p + qe, tp + (int64_t)td * te, -1, -td, qe + 1, te + 1},
+                            nullptr, rs, ri, rj);
       qs = qe - min(ri, qe);
       ts = te - min(rj, te);
     }
@@ -361,22 +399,34 @@ __device__ __forceinline__ AlWindow al_window(const AlignArgs& a, size_t k) {
 }
 
 // Pass C: the direction store of each window.
-template <bool GOTOH, bool SET>
+template <bool GOTOH, bool SET, bool STRAND = false>
 __global__ void __launch_bounds__(256) align_dirs(const AlignArgs a) {
+  static_assert(SET || !STRAND, "the strand kernels are set kernels");
   __shared__ uint2 lp[4][AL_LETTERS][64];
-  __shared__ int8_t smat[AL_LETTERS * AL_LETTERS];
-  al_load_matrix(a, smat);
+  __shared__ int8_t smats[STRAND ? 2 : 1][AL_LETTERS * AL_LETTERS];
+  if constexpr (STRAND) al_load_matrices(a, smats);
+  else al_load_matrix(a, smats[0]);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const size_t gw = (size_t)blockIdx.x * 4 + wave, GW = (size_t)gridDim.x * 4;
   uint2* const scr[2] = {a.scratch + gw * 2 * a.scols, a.scratch + gw * 2 * a.scols + a.scols};
   for (size_t k = gw; k < a.count; k += GW) {
     const AlWindow w = al_window<SET, true>(a, k);
     if (!w.ok) continue;
-    const uint8_t* tp = a.res + a.offs[a.out[w.h].index] + w.ts;
+    const uint64_t t = a.out[w.h].index;
+    const uint8_t* tp = a.res + a.offs[t] + w.ts;
+    int32_t td = 1;
+    const int8_t* smat = smats[0];
+    if constexpr (STRAND) {
+      if (__builtin_amdgcn_readfirstlane((int)al_reverse(a, w.h, t))) {
+        tp = a.res + a.offs[t] + (a.lens[t] - 1 - w.ts);
+        td = -1;
+        smat = smats[1];
+      }
+    }
     int32_t b0;
     uint32_t b1, b2;
     al_walk<GOTOH, true>(a, smat, lp[wave], scr,
-                         AlSeq{w.qp + w.qs, tp, 1, 1,
+                         AlSeq{w.qp + w.qs, tp, 1, td,
                                (uint32_t)__builtin_amdgcn_readfirstlane(w.Q),
                                (uint32_t)__builtin_amdgcn_readfirstlane(w.L)},
                          a.dirs + w.dir_off, b0, b1, b2);
@@ -385,14 +435,20 @@ __global__ void __launch_bounds__(256) align_dirs(const AlignArgs a) {
 
 // Pass D: one lane per hit follows the bits from the end cell to the start cell, counts columns
 // and identities, emits run-length ops backwards and reverses them in place.
-template <bool GOTOH, bool SET>
+template <bool GOTOH, bool SET, bool STRAND = false>
 __global__ void __launch_bounds__(64) align_path(const AlignArgs a) {
+  static_assert(SET || !STRAND, "the strand kernels are set kernels");
   const size_t k = (size_t)blockIdx.x * 64 + threadIdx.x;
   if (k >= a.count) return;
   const AlWindow w = al_window<SET, false>(a, k);
   if (!w.ok || w.cig_cap == 0) return;
   sw_alignment& r = a.out[w.h];
   const uint8_t* tp = a.res + a.offs[r.index] + w.ts;
+  [[maybe_unused]] bool rv = false;  // the reverse strand: column j is the complement of tp[-j]
+  if constexpr (STRAND) {
+    rv = al_reverse(a, w.h, r.index);
+    if (rv) tp = a.res + a.offs[r.index] + (a.lens[r.index] - 1 - w.ts);
+  }
   const uint8_t* qp = w.qp + w.qs;
   const uint8_t* db = reinterpret_cast<const uint8_t*>(a.dirs + w.dir_off);
   uint32_t* cig = a.cigar + w.cig_off;
@@ -424,7 +480,8 @@ __global__ void __launch_bounds__(64) align_path(const AlignArgs a) {
     }
     if (state == 3) {
       emit(SW_CIGAR_M);
-      idn += qp[i] == tp[j];
+      if constexpr (STRAND) idn += qp[i] == (rv ? al_comp(tp[-j]) : (uint32_t)tp[j]);
+      else idn += qp[i] == tp[j];
       if (i == 0 && j == 0) {
         done = true;
         break;
@@ -472,6 +529,20 @@ __global__ void __launch_bounds__(64) align_path(const AlignArgs a) {
   r.n_identities = idn;
   r.cigar_len = nops;
 }
+
+// After the last pass: a reverse-strand hit gets SW_ALIGN_REVERSE and, when it scored, its
+// target coordinates on the forward target (t_start = L - 1 - t_end', t_end = L - 1 - t_start').
+__global__ void __launch_bounds__(256) align_flip(const AlignArgs a) {
+  const size_t h = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (h >= a.n_hits) return;
+  sw_alignment& r = a.out[h];
+  if ((r.flags & (uint32_t)SW_ALIGN_NO_HIT) || !al_reverse(a, h, r.index)) return;
+  r.flags |= (uint32_t)SW_ALIGN_REVERSE;
+  if (r.score <= 0) return;
+  const uint32_t L = a.lens[r.index], ts = r.t_start, te = r.t_end;
+  r.t_start = L - 1 - te;
+  r.t_end = L - 1 - ts;
+}
 }  // namespace swk
 
 extern "C" uint64_t swk_align_dir_dwords(uint32_t rows, uint32_t cols) {
@@ -504,6 +575,8 @@ static swk::AlignArgs align_args(const SwkAlign* p) {
   a.nq = p->nq;
   a.hits_per_query = p->hits_per_query;
   a.n = p->n;
+  a.strands = p->strands;
+  a.strand_by_hit = p->strand_by_hit ? 1u : 0u;
   return a;
 }
 
@@ -511,7 +584,8 @@ static bool align_args_ok(const SwkAlign* p) {
   return p && p->alpha >= 1 && p->alpha < (uint32_t)swk::AL_LETTERS &&
          p->pad < (uint32_t)swk::AL_LETTERS && p->waves && p->waves % 4 == 0 && p->scols &&
          (!p->set || (p->qtab && p->nq && (p->hit_queries != nullptr) != (p->hits_per_query != 0) &&
-                      p->n_hits <= 0xFFFFFFFFull));
+                      p->n_hits <= 0xFFFFFFFFull)) &&
+         (!p->strands || p->set);
 }
 
 // Passes A and B for hits [0, n_hits): every record written, paths left out.
@@ -521,7 +595,11 @@ extern "C" hipError_t swk_launch_align_ends(const SwkAlign* p, hipStream_t st) {
   const swk::AlignArgs a = align_args(p);
   const dim3 grid((unsigned)(p->waves / 4));
   // (the single-query kernels are their own instantiation: the set's lookups cost them nothing)
-  if (p->gotoh && p->set)
+  if (p->strands && p->gotoh)
+    hipLaunchKernelGGL((swk::align_ends<true, true, true>), grid, dim3(256), 0, st, a);
+  else if (p->strands)
+    hipLaunchKernelGGL((swk::align_ends<false, true, true>), grid, dim3(256), 0, st, a);
+  else if (p->gotoh && p->set)
     hipLaunchKernelGGL((swk::align_ends<true, true>), grid, dim3(256), 0, st, a);
   else if (p->gotoh)
     hipLaunchKernelGGL((swk::align_ends<true, false>), grid, dim3(256), 0, st, a);
@@ -548,7 +626,13 @@ extern "C" hipError_t swk_launch_align_paths(const SwkAlign* p, const uint32_t* 
   a.dirs = dirs;
   const dim3 grid((unsigned)(std::min<size_t>(p->waves, (count + 3) / 4 * 4) / 4));
   const dim3 pgrid((unsigned)((count + 63) / 64));
-  if (p->gotoh && p->set) {
+  if (p->strands && p->gotoh) {
+    hipLaunchKernelGGL((swk::align_dirs<true, true, true>), grid, dim3(256), 0, st, a);
+    hipLaunchKernelGGL((swk::align_path<true, true, true>), pgrid, dim3(64), 0, st, a);
+  } else if (p->strands) {
+    hipLaunchKernelGGL((swk::align_dirs<false, true, true>), grid, dim3(256), 0, st, a);
+    hipLaunchKernelGGL((swk::align_path<false, true, true>), pgrid, dim3(64), 0, st, a);
+  } else if (p->gotoh && p->set) {
     hipLaunchKernelGGL((swk::align_dirs<true, true>), grid, dim3(256), 0, st, a);
     hipLaunchKernelGGL((swk::align_path<true, true>), pgrid, dim3(64), 0, st, a);
   } else if (p->gotoh) {
@@ -561,5 +645,16 @@ extern "C" hipError_t swk_launch_align_paths(const SwkAlign* p, const uint32_t* 
     hipLaunchKernelGGL((swk::align_dirs<false, false>), grid, dim3(256), 0, st, a);
     hipLaunchKernelGGL((swk::align_path<false, false>), pgrid, dim3(64), 0, st, a);
   }
+  return hipGetLastError();
+}
+
+// The strand call's last launch: SW_ALIGN_REVERSE and the forward target coordinates of the
+// reverse-strand hits of [0, n_hits).
+extern "C" hipError_t swk_launch_align_flip(const SwkAlign* p, hipStream_t st) {
+  if (!p || p->n_hits == 0 || !p->strands) return hipSuccess;
+  if (!align_args_ok(p)) return hipErrorInvalidValue;
+  const swk::AlignArgs a = align_args(p);
+  hipLaunchKernelGGL(swk::align_flip, dim3((unsigned)((p->n_hits + 255) / 256)), dim3(256), 0, st,
+                     a);
   return hipGetLastError();
 }

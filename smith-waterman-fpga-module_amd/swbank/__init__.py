@@ -52,6 +52,8 @@ EXPORTS = (
     "sw_shuffle_batch_device", "sw_score_histogram_device", "sw_fit_statistics",
     "sw_estimate_statistics", "sw_estimate_statistics_device",
     "sw_hit_significance", "sw_hit_significance_device",
+    "sw_revcomp_codes", "sw_revcomp_batch_device", "sw_score_strands",
+    "sw_score_strands_device", "sw_align_strand_hits", "sw_align_strand_hits_device",
 )
 ABI_VERSION = 6
 COUNTERS = ("stream_calls", "stream_reruns", "stream_declined", "chunked_calls", "device_sorts",
@@ -62,6 +64,7 @@ MAX_DEVICES = 16
 CIGAR_M, CIGAR_I, CIGAR_D = 0, 1, 2          # BAM codes: I consumes query only, D target only
 ALIGN_EMPTY, ALIGN_NO_PATH = 1, 2            # sw_alignment.flags
 ALIGN_NO_HIT = 4                             # ... the slot named no pair (with ALIGN_EMPTY)
+ALIGN_REVERSE = 8                            # ... aligned against the target's reverse complement
 RECORD_BYTES, RECORD_MAX_BASES = 64, 232
 TOP_MAX_K = 4096                             # SW_TOP_MAX_K: the largest k of the top-hits calls
 HIT_NONE = 0xFFFFFFFFFFFFFFFF                # SW_HIT_NONE: a hit slot past the row's count
@@ -142,7 +145,13 @@ class Alignment:
 
     @property
     def has_path(self) -> bool:
-        return self.flags == 0
+        return self.flags & ~ALIGN_REVERSE == 0
+
+    @property
+    def reverse(self) -> bool:
+        """The hit lies on the reverse strand (ALIGN_REVERSE): aligned against the reverse
+        complement of its target, t_start / t_end given on the forward target."""
+        return bool(self.flags & ALIGN_REVERSE)
 
 
 def cigar_string(ops) -> str:
@@ -159,7 +168,7 @@ def alignments_from(records: np.ndarray, cigar: np.ndarray) -> list:
     out = []
     for r in records:
         ops = ()
-        if r["flags"] == 0:
+        if int(r["flags"]) & ~ALIGN_REVERSE == 0:
             ops = tuple(int(x) for x in cigar[int(r["cigar_offset"]):
                                               int(r["cigar_offset"]) + int(r["cigar_len"])])
         out.append(Alignment(int(r["index"]), int(r["id"]), int(r["score"]), int(r["flags"]),
@@ -251,6 +260,13 @@ def lib() -> ctypes.CDLL:
         "sw_estimate_statistics": (i32, [P, P, sz, P, P, sz, u64, u32, P]),
         "sw_hit_significance": (i32, [P, P, P, sz, u64, P, P]),
         "sw_hit_significance_device": (i32, [P, P, P, P, P, sz, sz, u64, P, P, P]),
+        "sw_revcomp_codes": (sz, [P, sz, P]),
+        "sw_revcomp_batch_device": (i32, [P, P, P, P, sz, P, P]),
+        "sw_score_strands": (i32, [P, P, sz, P, P, sz, P, P]),
+        "sw_score_strands_device": (i32, [P, P, P, P, P, sz, u32, u32, P, P, P]),
+        "sw_align_strand_hits": (i32, [P, P, sz, P, P, P, sz, P, P, sz, P, sz, P, P, sz, P]),
+        "sw_align_strand_hits_device": (i32, [P, P, P, P, P, sz, u32, P, P, sz, P, sz, P, P, u32,
+                                              P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -322,6 +338,15 @@ def make_records(seqs: Sequence[np.ndarray], ids: Optional[Sequence[int]] = None
         q[:len(c)] = c
         q = q.reshape(-1, 4)
         out[k, 6:6 + len(q)] = q[:, 0] | q[:, 1] << 2 | q[:, 2] << 4 | q[:, 3] << 6
+    return out
+
+
+def revcomp(codes) -> np.ndarray:
+    """sw_revcomp_codes: the reverse complement of DNA codes (T <-> A, C <-> G; N stays N)."""
+    a = np.ascontiguousarray(codes, dtype=np.uint8).reshape(-1)
+    out = np.empty(a.size, dtype=np.uint8)
+    if a.size:
+        lib().sw_revcomp_codes(_p(a), a.size, _p(out))
     return out
 
 
@@ -762,6 +787,89 @@ class ScoreBank:
                                                      hits_per_query, len(stats), db_size,
                                                      d_bits or None, d_evalues or None,
                                                      stream or None))
+
+    # both DNA strands: reverse complement, strand-merged scores, strand-aware alignments
+    def revcomp_batch_device(self, d_res: int, d_offs: int, d_lens: int, n: int, d_out: int,
+                             stream: int = 0):
+        """sw_revcomp_batch_device: device pointers (ints); d_out[d_offs[k] .. + d_lens[k])
+        receives the reverse complement of target k, nothing else of d_out is written.  Async on
+        `stream` (0: the bank's own stream; sync() before reading)."""
+        self._check(lib().sw_revcomp_batch_device(self._h, d_res or None, d_offs or None,
+                                                  d_lens or None, n, d_out or None,
+                                                  stream or None))
+
+    def score_strands_device(self, d_res: int, d_offs: int, d_lens: int, n: int, max_len: int,
+                             d_scores: int, d_strands: int = 0, d_rc: int = 0, min_len: int = 0,
+                             stream: int = 0):
+        """sw_score_strands_device: device pointers (ints); d_scores receives the nq x n int32
+        strand-merged scores, d_strands (optional) the nq x n uint8 strands (1: the reverse
+        score is strictly greater).  d_rc: the caller's resident reverse complement at the same
+        offsets (0: the bank makes it in its scratch).  Async on `stream`."""
+        self._check(lib().sw_score_strands_device(self._h, d_res or None, d_rc or None,
+                                                  d_offs or None, d_lens or None, n, min_len,
+                                                  max_len, d_scores or None, d_strands or None,
+                                                  stream or None))
+
+    def score_strands(self, residues: np.ndarray, offsets: np.ndarray, lens: np.ndarray):
+        """sw_score_strands: (scores int32, strands uint8) of the host batch on both strands,
+        [n] for one loaded query, [nq, n] for a query set."""
+        res, offs, ln, _ = validate_batch(residues, offsets, lens)
+        nq, n = max(self.query_count(), 1), len(ln)
+        sc = np.zeros(nq * max(n, 1), np.int32)
+        sd = np.zeros(nq * max(n, 1), np.uint8)
+        self._check(lib().sw_score_strands(self._h, _p(res), res.size, _p(offs), _p(ln), n,
+                                           _p(sc), _p(sd)))
+        scores = sc[:nq * n].reshape(nq, n)
+        strands = sd[:nq * n].reshape(nq, n)
+        return (scores[0], strands[0]) if nq == 1 else (scores, strands)
+
+    def align_strand_hits(self, residues: np.ndarray, offsets: np.ndarray, lens: np.ndarray,
+                          strands=None, hits=None, hit_queries=None, hits_per_query: int = 0,
+                          ids: Optional[np.ndarray] = None, cigar_cap: Optional[int] = None,
+                          n_hits: Optional[int] = None) -> list:
+        """sw_align_strand_hits: align_set_hits with the [nq, n] strand matrix of score_strands
+        (None: every hit on the forward strand).  A hit on the reverse strand is aligned against
+        the reverse complement of its target: Alignment.reverse is set and t_start / t_end are
+        given on the forward target."""
+        res, offs, ln, idv = validate_batch(residues, offsets, lens, ids)
+        sv = None
+        if strands is not None:
+            sv = np.ascontiguousarray(strands, dtype=np.uint8).reshape(-1)
+            if sv.size != max(self.query_count(), 1) * len(ln):
+                raise ValueError("strands: nq x n entries")
+        hv = None if hits is None else np.ascontiguousarray(hits, dtype=np.uint64).reshape(-1)
+        hq = None if hit_queries is None else \
+            np.ascontiguousarray(hit_queries, dtype=np.uint32).reshape(-1)
+        if n_hits is None:
+            n_hits = len(hv) if hv is not None else len(hq) if hq is not None else len(ln)
+        if (hv is not None and len(hv) < n_hits) or (hq is not None and len(hq) < n_hits):
+            raise ValueError("hits / hit_queries shorter than n_hits")
+        out = np.zeros(max(n_hits, 1), dtype=ALIGNMENT_DTYPE)
+        if cigar_cap is None:  # runs alternate with M runs: at most 2 x columns + 1 ops a path
+            tv = hv[:n_hits] if hv is not None else np.arange(min(n_hits, len(ln)), dtype=np.uint64)
+            sel = tv[tv < len(ln)].astype(np.int64)
+            cigar_cap = 2 * int(ln[sel].astype(np.int64).sum()) + n_hits
+        cig = np.zeros(max(cigar_cap, 1), dtype=np.uint32)
+        used = ctypes.c_size_t()
+        self._check(lib().sw_align_strand_hits(
+            self._h, _p(res), res.size, _p(offs), _p(ln), _p(idv) if idv is not None else None,
+            len(ln), _p(sv) if sv is not None else None, _p(hq) if hq is not None else None,
+            hits_per_query, _p(hv) if hv is not None else None, n_hits, _p(out),
+            _p(cig) if cigar_cap else None, cigar_cap, ctypes.byref(used)))
+        return alignments_from(out[:n_hits], cig)
+
+    def align_strand_hits_device(self, d_res: int, d_offs: int, d_lens: int, n: int, max_len: int,
+                                 n_hits: int, d_out: int, d_strands: int = 0, d_hits: int = 0,
+                                 d_hit_queries: int = 0, hits_per_query: int = 0,
+                                 d_cigar: int = 0, cigar_stride: int = 0, stream: int = 0,
+                                 d_ids: int = 0):
+        """sw_align_strand_hits_device: align_set_hits_device with d_strands, the nq x n uint8
+        strand matrix score_strands_device writes (0: every hit on the forward strand).  Async on
+        `stream` (0: the bank's own stream; sync() before reading)."""
+        self._check(lib().sw_align_strand_hits_device(
+            self._h, d_res or None, d_offs or None, d_lens or None, d_ids or None, n, max_len,
+            d_strands or None, d_hit_queries or None, hits_per_query, d_hits or None, n_hits,
+            d_out or None, d_cigar or None, cigar_stride, stream or None))
 
     def counters(self) -> dict:
         """sw_bank_counters: feeder / fallback counts since the bank was created."""
