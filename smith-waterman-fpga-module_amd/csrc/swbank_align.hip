@@ -118,20 +118,6 @@ sw_status align_block(sw_bank* b, SwkAlign& p, size_t nh, uint32_t max_len) {
   return SW_OK;
 }
 
-// Passes C and D in slots of the largest possible window (the device call: nothing read back).
-sw_status paths_by_slot(sw_bank* b, const SwkAlign& p, uint32_t max_len, hipStream_t hs,
-                        size_t& chunks) {
-  chunks = 0;
-  const uint64_t slot = swk_align_dir_dwords(p.qlen, max_len), budget = dir_budget();
-  if (slot == 0 || slot > budget) return SW_OK;  // every non-empty hit keeps SW_ALIGN_NO_PATH
-  const size_t per = (size_t)std::min<uint64_t>(budget / slot, p.n_hits);
-  HIPOK(b, b->al_dirs.reserve((size_t)(slot * per)));
-  for (size_t h0 = 0; h0 < p.n_hits; h0 += per, ++chunks)
-    HIPOK(b, swk_launch_align_paths(&p, nullptr, h0, std::min(per, p.n_hits - h0), nullptr, slot,
-                                    b->al_dirs.p, hs));
-  return SW_OK;
-}
-
 void name_kernel(sw_bank* b, bool set, size_t hits, size_t chunks, bool strand = false) {
   if (strand)
     snprintf(b->last_kernel, sizeof(b->last_kernel), "align-strand i32 nq=%zu hits=%zu chunks=%zu",
@@ -141,6 +127,43 @@ void name_kernel(sw_bank* b, bool set, size_t hits, size_t chunks, bool strand =
              query_count(b), hits, chunks);
   else
     snprintf(b->last_kernel, sizeof(b->last_kernel), "align i32 hits=%zu chunks=%zu", hits, chunks);
+}
+
+// How every entry opens: a strand call is for DNA banks; a multi-device bank checks the state it
+// holds itself and hands the call to its root (call(root, stream)), where the caller's buffers
+// are.  False on a single bank that may go on; else the call is over and `st` is its status.
+template <class F>
+bool align_opening(sw_bank* b, const Pairs& pr, void* stream, sw_status& st, F&& call) {
+  if (pr.strand_call && b->cfg.alphabet != SW_ALPHABET_DNA) {
+    st = fail(b, SW_ERR_UNSUPPORTED, "strand alignments: DNA banks only");
+    return true;
+  }
+  if (!b->is_multi()) return false;
+  if (!b->have_query)
+    st = fail(b, SW_ERR_STATE, "penalties or query not loaded");
+  else if (!pr.set && b->qset.size() > 1)
+    st = fail(b, SW_ERR_STATE, "a query set is loaded: alignments take one query");
+  else
+    on_root(b, stream, st, call);
+  return true;
+}
+
+// Passes C and D of a device call in slots of the largest possible window (nothing is read
+// back); a window past the budget: every non-empty hit keeps SW_ALIGN_NO_PATH.
+sw_status paths_by_slot(sw_bank* b, const SwkAlign& p, uint32_t max_len, hipStream_t hs,
+                        size_t& chunks) {
+  const uint64_t slot = swk_align_dir_dwords(p.qlen, max_len), budget = dir_budget();
+  const size_t per =
+      slot == 0 || slot > budget ? 0 : (size_t)std::min<uint64_t>(budget / slot, p.n_hits);
+  if (per) HIPOK(b, b->al_dirs.reserve((size_t)(slot * per)));
+  return timed_on(b, hs, [&] {
+    for (size_t h0 = 0; per && h0 < p.n_hits; h0 += per, ++chunks) {
+      const hipError_t e = swk_launch_align_paths(&p, nullptr, h0, std::min(per, p.n_hits - h0),
+                                                  nullptr, slot, b->al_dirs.p, hs);
+      if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+  });
 }
 
 sw_status device_launch(sw_bank* b, const uint8_t* d_res, const uint64_t* d_offs,
@@ -165,47 +188,31 @@ sw_status device_launch(sw_bank* b, const uint8_t* d_res, const uint64_t* d_offs
   if (st != SW_OK) return st;
   HIPOK(b, hipStreamWaitEvent(hs, b->ev_ready, 0));  // the queries' codes are uploaded
   HIPOK(b, hipStreamWaitEvent(hs, b->ev_used, 0));   // bank scratch is free
-  Timed ab{b, hs};
-  if ((st = ab.begin()) != SW_OK) return st;
-  HIPOK(b, swk_launch_align_ends(&p, hs));
-  if ((st = ab.end()) != SW_OK) return st;
+  if ((st = timed_on(b, hs, [&] { return swk_launch_align_ends(&p, hs); })) != SW_OK) return st;
   size_t chunks = 0;
-  if (p.cigar_stride) {
-    Timed cd{b, hs};
-    if ((st = cd.begin()) != SW_OK) return st;
-    if ((st = paths_by_slot(b, p, max_len, hs, chunks)) != SW_OK) return st;
-    if ((st = cd.end()) != SW_OK) return st;
-  }
+  if (p.cigar_stride && (st = paths_by_slot(b, p, max_len, hs, chunks)) != SW_OK) return st;
   HIPOK(b, swk_launch_align_flip(&p, hs));  // (a strand call: after the last pass)
   HIPOK(b, hipEventRecord(b->ev_used, hs));
   name_kernel(b, pr.set, pr.n_hits, chunks, pr.strand_call);
   return SW_OK;
 }
 
-// sw_align_hits_device and sw_align_set_hits_device.
+// sw_align_hits_device, sw_align_set_hits_device and sw_align_strand_hits_device.
 sw_status device_call(sw_bank* b, const uint8_t* d_res, const uint64_t* d_offs,
                       const uint32_t* d_lens, const uint64_t* d_ids, size_t n, uint32_t max_len,
                       const Pairs& pr, sw_alignment* d_out, uint32_t* d_cigar,
                       uint32_t cigar_stride, void* stream) {
   DevGuard dev_guard(b);  // on the bank's device; the caller's is restored on return (ABI 6)
   if (!b) return SW_ERR_ARG;
-  if (pr.strand_call && b->cfg.alphabet != SW_ALPHABET_DNA)
-    return fail(b, SW_ERR_UNSUPPORTED, "strand alignments: DNA banks only");
-  if (b->is_multi()) {  // on the root device, where the caller's buffers are
-    sw_bank* k = b->kids[0];
-    if (!b->have_query) return fail(b, SW_ERR_STATE, "penalties or query not loaded");
-    if (!pr.set && b->qset.size() > 1)
-      return fail(b, SW_ERR_STATE, "a query set is loaded: alignments take one query");
-    const sw_status st = device_call(k, d_res, d_offs, d_lens, d_ids, n, max_len, pr, d_out,
-                                     d_cigar, cigar_stride, stream ? stream : k->stream);
-    if (st != SW_OK) return fail(b, st, "device %d: %s", k->device, k->err);
-    snprintf(b->last_kernel, sizeof(b->last_kernel), "%s", k->last_kernel);
-    return SW_OK;
-  }
+  sw_status st;
+  if (align_opening(b, pr, stream, st, [&](sw_bank* r, void* s) {
+        return device_call(r, d_res, d_offs, d_lens, d_ids, n, max_len, pr, d_out, d_cigar,
+                           cigar_stride, s);
+      }))
+    return st;
   // a hand-off fault latched by an earlier device call is returned before anything runs
   if (const sw_status fs = take_fault(b, 0); fs != SW_OK) return fs;
-  sw_status st = align_ready(b, pr.set);
-  if (st != SW_OK) return st;
+  if ((st = align_ready(b, pr.set)) != SW_OK) return st;
   if (pr.n_hits == 0) return SW_OK;
   if (!d_res || !d_offs || !d_lens || (!pr.set && !pr.hits) || !d_out || n == 0)
     return fail(b, SW_ERR_ARG, "null device buffer or an empty batch");
@@ -213,83 +220,73 @@ sw_status device_call(sw_bank* b, const uint8_t* d_res, const uint64_t* d_offs,
   if (d_cigar && cigar_stride && (uint64_t)pr.n_hits * cigar_stride > 0xFFFFFFFFull)
     return fail(b, SW_ERR_ARG, "n_hits x cigar_stride must fit 32 bits (cigar_offset)");
   HIPOK(b, hipSetDevice(b->device));
-  hipStream_t hs = stream ? reinterpret_cast<hipStream_t>(stream) : b->stream;
   return device_launch(b, d_res, d_offs, d_lens, d_ids, n, max_len, pr, d_out, d_cigar,
-                       cigar_stride, hs);
+                       cigar_stride, stream_or(b, stream));
 }
 
-// sw_align_hits and sw_align_set_hits.
-sw_status host_call(sw_bank* b, const uint8_t* residues, size_t residues_len,
-                    const uint64_t* offsets, const uint32_t* lens, const uint64_t* ids, size_t n,
-                    const Pairs& pr, sw_alignment* out, uint32_t* cigar, size_t cigar_cap,
-                    size_t* cigar_used) {
-  DevGuard dev_guard(b);  // on the bank's device; the caller's is restored on return (ABI 6)
-  if (!b) return SW_ERR_ARG;
-  if (cigar_used) *cigar_used = 0;
-  if (pr.strand_call && b->cfg.alphabet != SW_ALPHABET_DNA)
-    return fail(b, SW_ERR_UNSUPPORTED, "strand alignments: DNA banks only");
-  if (b->is_multi()) {  // on the root device: hit lists are small
-    sw_bank* k = b->kids[0];
-    if (!b->have_query) return fail(b, SW_ERR_STATE, "penalties or query not loaded");
-    if (!pr.set && b->qset.size() > 1)
-      return fail(b, SW_ERR_STATE, "a query set is loaded: alignments take one query");
-    const sw_status st = host_call(k, residues, residues_len, offsets, lens, ids, n, pr, out, cigar,
-                                   cigar_cap, cigar_used);
-    if (st != SW_OK) return fail(b, st, "device %d: %s", k->device, k->err);
-    snprintf(b->last_kernel, sizeof(b->last_kernel), "%s", k->last_kernel);
-    return SW_OK;
-  }
-  sw_status st = align_ready(b, pr.set);
-  if (st != SW_OK) return st;
-  const size_t n_hits = pr.n_hits;
-  if (n_hits == 0) return SW_OK;
-  if (!offsets || !lens || (!pr.set && !pr.hits) || !out)
-    return fail(b, SW_ERR_ARG, "null host buffer");
-  if ((st = check_pairs(b, pr, n)) != SW_OK) return st;
-  // validate and gather the listed targets (a repeated hit is gathered again); a set call also
-  // lists each hit's query (SW_QUERY_NONE for a slot that names no pair: nothing is gathered)
-  const size_t nq = query_count(b);
-  const auto target_of = [&](size_t h) { return pr.hits ? pr.hits[h] : (uint64_t)h; };
-  std::vector<uint64_t> goffs(n_hits);
-  std::vector<uint32_t> glens(n_hits), gq(pr.set ? n_hits : 0);
-  std::vector<uint8_t> gs(pr.strands ? n_hits : 0);  // a strand call: each hit's strand
-  uint64_t total = 0;
+// ---- the host calls, step by step ---------------------------------------------------------
+// The listed hits of a host call, gathered: hit h's codes at res[offs[h]], lens[h] of them, (a
+// set call) its query q[h], SW_QUERY_NONE for a slot that names no pair (nothing is gathered),
+// (a strand call) its strand s[h].  A repeated hit is gathered again.
+struct Gathered {
+  std::vector<uint64_t> offs;
+  std::vector<uint32_t> lens, q;
+  std::vector<uint8_t> s, res;
   uint32_t max_len = 0;
+};
+
+uint64_t target_of(const Pairs& pr, size_t h) { return pr.hits ? pr.hits[h] : (uint64_t)h; }
+
+// Step 1: validate and gather the listed targets.
+sw_status gather_hits(sw_bank* b, const uint8_t* residues, size_t residues_len,
+                      const uint64_t* offsets, const uint32_t* lens, size_t n, const Pairs& pr,
+                      Gathered& g) {
+  const size_t n_hits = pr.n_hits, nq = query_count(b);
+  g.offs.resize(n_hits);
+  g.lens.resize(n_hits);
+  g.q.resize(pr.set ? n_hits : 0);
+  g.s.resize(pr.strands ? n_hits : 0);
+  uint64_t total = 0;
   for (size_t h = 0; h < n_hits; ++h) {
-    const uint64_t t = target_of(h);
-    goffs[h] = total;
-    glens[h] = 0;
+    const uint64_t t = target_of(pr, h);
+    g.offs[h] = total;
+    g.lens[h] = 0;
     if (pr.set) {
       const uint32_t qi = pr.hit_queries ? pr.hit_queries[h] : (uint32_t)(h / pr.hits_per_query);
-      gq[h] = qi == SW_QUERY_NONE || t == SW_HIT_NONE ? SW_QUERY_NONE : qi;
+      g.q[h] = qi == SW_QUERY_NONE || t == SW_HIT_NONE ? SW_QUERY_NONE : qi;
       if (qi != SW_QUERY_NONE && qi >= nq)
         return fail(b, SW_ERR_ARG, "hit %zu: query %u >= nq = %zu", h, qi, nq);
       if (t == SW_HIT_NONE) continue;
     }
     if (t >= n) return fail(b, SW_ERR_ARG, "hit %zu: target %llu >= n = %zu", h,
                             (unsigned long long)t, n);
-    if (pr.set && gq[h] == SW_QUERY_NONE) continue;
+    if (pr.set && g.q[h] == SW_QUERY_NONE) continue;
     const uint64_t o = offsets[t], l = lens[t];
     if (l && (!residues || o > residues_len || l > residues_len - o))
       return fail(b, SW_ERR_ARG, "target %llu outside the residues", (unsigned long long)t);
-    glens[h] = (uint32_t)l;
-    if (pr.strands) gs[h] = pr.strands[(size_t)gq[h] * n + t] != 0;
+    g.lens[h] = (uint32_t)l;
+    if (pr.strands) g.s[h] = pr.strands[(size_t)g.q[h] * n + t] != 0;
     total += l;
-    max_len = std::max(max_len, (uint32_t)l);
+    g.max_len = std::max(g.max_len, (uint32_t)l);
   }
-  std::vector<uint8_t> gres(std::max<uint64_t>(total, 1), 0);
+  g.res.assign(std::max<uint64_t>(total, 1), 0);
   for (size_t h = 0; h < n_hits; ++h) {
-    const uint8_t* src = glens[h] ? residues + offsets[target_of(h)] : nullptr;
-    for (uint32_t i = 0; i < glens[h]; ++i) {
+    const uint8_t* src = g.lens[h] ? residues + offsets[target_of(pr, h)] : nullptr;
+    for (uint32_t i = 0; i < g.lens[h]; ++i) {
       if (src[i] >= (uint32_t)b->alpha)
         return fail(b, SW_ERR_ARG, "target %llu code %u at %u outside alphabet %d",
-                    (unsigned long long)target_of(h), src[i], i, b->alpha);
-      gres[goffs[h] + i] = src[i];
+                    (unsigned long long)target_of(pr, h), src[i], i, b->alpha);
+      g.res[g.offs[h] + i] = src[i];
     }
   }
-  HIPOK(b, hipSetDevice(b->device));
-  hipStream_t hs = b->stream;
-  HIPOK(b, b->al_res.reserve(gres.size()));
+  return SW_OK;
+}
+
+// Step 2: the gathered batch on the device (hit h is target h against query al_hq[h], on strand
+// al_hs[h]) and the launch block over it.
+sw_status stage_hits(sw_bank* b, const Pairs& pr, const Gathered& g, SwkAlign& p, hipStream_t hs) {
+  const size_t n_hits = pr.n_hits;
+  HIPOK(b, b->al_res.reserve(g.res.size()));
   HIPOK(b, b->al_offs.reserve(n_hits));
   HIPOK(b, b->al_lens.reserve(n_hits));
   HIPOK(b, b->al_out.reserve(n_hits));
@@ -297,127 +294,178 @@ sw_status host_call(sw_bank* b, const uint8_t* residues, size_t residues_len,
   if (pr.strands) HIPOK(b, b->al_hs.reserve(n_hits));
   HIPOK(b, hipStreamWaitEvent(hs, b->ev_ready, 0));
   HIPOK(b, hipStreamWaitEvent(hs, b->ev_used, 0));  // an earlier call may still read the buffers
-  HIPOK(b, hipMemcpyAsync(b->al_res.p, gres.data(), gres.size(), hipMemcpyHostToDevice, hs));
-  HIPOK(b, hipMemcpyAsync(b->al_offs.p, goffs.data(), n_hits * 8, hipMemcpyHostToDevice, hs));
-  HIPOK(b, hipMemcpyAsync(b->al_lens.p, glens.data(), n_hits * 4, hipMemcpyHostToDevice, hs));
+  HIPOK(b, hipMemcpyAsync(b->al_res.p, g.res.data(), g.res.size(), hipMemcpyHostToDevice, hs));
+  HIPOK(b, hipMemcpyAsync(b->al_offs.p, g.offs.data(), n_hits * 8, hipMemcpyHostToDevice, hs));
+  HIPOK(b, hipMemcpyAsync(b->al_lens.p, g.lens.data(), n_hits * 4, hipMemcpyHostToDevice, hs));
   if (pr.set)
-    HIPOK(b, hipMemcpyAsync(b->al_hq.p, gq.data(), n_hits * 4, hipMemcpyHostToDevice, hs));
+    HIPOK(b, hipMemcpyAsync(b->al_hq.p, g.q.data(), n_hits * 4, hipMemcpyHostToDevice, hs));
   if (pr.strands)
-    HIPOK(b, hipMemcpyAsync(b->al_hs.p, gs.data(), n_hits, hipMemcpyHostToDevice, hs));
-  __atomic_fetch_add(&b->ctr.h2d_bytes, gres.size() + n_hits * (pr.set ? 16 : 12),
+    HIPOK(b, hipMemcpyAsync(b->al_hs.p, g.s.data(), n_hits, hipMemcpyHostToDevice, hs));
+  __atomic_fetch_add(&b->ctr.h2d_bytes, g.res.size() + n_hits * (pr.set ? 16 : 12),
                      __ATOMIC_RELAXED);
-  SwkAlign p{};
   p.res = b->al_res.p;
   p.offs = b->al_offs.p;
   p.lens = b->al_lens.p;
   p.out = b->al_out.p;
-  if (pr.set) {  // the gathered batch: hit h is target h against query al_hq[h]
+  if (pr.set) {
     p.set = 1;
     p.n = n_hits;
     p.hit_queries = b->al_hq.p;
   }
-  if (pr.strands) {  // ... on strand al_hs[h]
+  if (pr.strands) {
     p.strands = b->al_hs.p;
     p.strand_by_hit = 1;
   }
-  if ((st = align_block(b, p, n_hits, max_len)) != SW_OK) return st;
-  Timed ab{b, hs};
-  if ((st = ab.begin()) != SW_OK) return st;
-  HIPOK(b, swk_launch_align_ends(&p, hs));
-  if ((st = ab.end()) != SW_OK) return st;
+  return align_block(b, p, n_hits, g.max_len);
+}
+
+// Step 3: the CIGAR windows of pass A's records that fit the budget (dwords of direction store),
+// in hit order, in chunks that fit it together; each hit's ops in a slot of rows + columns of the
+// window (a path never has more ops).  A pure function of the records and the budget.
+struct Windows {
+  std::vector<uint32_t> list;      // the planned hits
+  std::vector<SwkAlignPlan> plan;  // ... and where each one's window and ops go
+  std::vector<size_t> cut{0};      // chunk c = positions [cut[c], cut[c + 1])
+  uint64_t most = 0, cig = 0;      // the largest chunk's dwords; ops slots in all
+};
+
+Windows plan_windows(const sw_alignment* out, size_t n_hits, uint64_t budget) {
+  Windows w;
+  uint64_t used = 0;
+  for (size_t h = 0; h < n_hits; ++h) {
+    const sw_alignment& r = out[h];
+    if (r.score <= 0) continue;
+    const uint32_t Q = r.q_end - r.q_start + 1, L = r.t_end - r.t_start + 1;
+    const uint64_t need = swk_align_dir_dwords(Q, L);
+    if (need > budget) continue;  // SW_ALIGN_NO_PATH, coordinates stay
+    if (used + need > budget) {
+      w.cut.push_back(w.list.size());
+      used = 0;
+    }
+    w.list.push_back((uint32_t)h);
+    w.plan.push_back(SwkAlignPlan{used, need, w.cig, Q + L, 0});
+    used += need;
+    w.most = std::max(w.most, used);
+    w.cig += (uint64_t)Q + L;
+  }
+  w.cut.push_back(w.list.size());
+  return w;
+}
+
+// Step 4: the ops back to back in hit order, as many as the caller's buffer takes; their count.
+size_t pack_ops(const Windows& w, const std::vector<uint32_t>& ops, sw_alignment* out,
+                size_t n_hits, uint32_t* cigar, size_t cigar_cap) {
+  size_t at = 0, k = 0;
+  for (size_t h = 0; h < n_hits; ++h) {
+    sw_alignment& r = out[h];
+    const bool planned = k < w.list.size() && w.list[k] == h;
+    const uint64_t from = planned ? w.plan[k].cig_off : 0;
+    if (planned) ++k;
+    r.cigar_offset = 0;
+    if (r.flags != 0 || !planned) continue;
+    if (r.cigar_len > cigar_cap - at) {
+      r.flags = SW_ALIGN_NO_PATH;
+      r.cigar_len = r.n_columns = r.n_identities = 0;
+      continue;
+    }
+    std::memcpy(cigar + at, ops.data() + from, (size_t)r.cigar_len * 4);
+    r.cigar_offset = (uint32_t)at;
+    at += r.cigar_len;
+  }
+  return at;
+}
+
+// Step 5: the records speak of the caller's batch: index, id, the reverse strand's coordinates.
+void rewrite_records(const Pairs& pr, const Gathered& g, const uint64_t* ids, bool with_cigar,
+                     sw_alignment* out) {
+  for (size_t h = 0; h < pr.n_hits; ++h) {
+    if (!with_cigar) out[h].cigar_offset = 0;
+    if (out[h].flags & SW_ALIGN_NO_HIT) continue;  // (index = id = SW_HIT_NONE)
+    const uint64_t t = target_of(pr, h);
+    out[h].index = t;
+    out[h].id = ids ? ids[t] : t;
+    if (pr.strands && g.s[h]) {  // the reverse strand: coordinates on the forward target
+      out[h].flags |= SW_ALIGN_REVERSE;
+      if (out[h].score > 0) {
+        const uint32_t ts = out[h].t_start, te = out[h].t_end;
+        out[h].t_start = g.lens[h] - 1 - te;
+        out[h].t_end = g.lens[h] - 1 - ts;
+      }
+    }
+  }
+}
+
+// sw_align_hits, sw_align_set_hits and sw_align_strand_hits.
+sw_status host_call(sw_bank* b, const uint8_t* residues, size_t residues_len,
+                    const uint64_t* offsets, const uint32_t* lens, const uint64_t* ids, size_t n,
+                    const Pairs& pr, sw_alignment* out, uint32_t* cigar, size_t cigar_cap,
+                    size_t* cigar_used) {
+  DevGuard dev_guard(b);  // on the bank's device; the caller's is restored on return (ABI 6)
+  if (!b) return SW_ERR_ARG;
+  if (cigar_used) *cigar_used = 0;
+  sw_status st;
+  if (align_opening(b, pr, nullptr, st, [&](sw_bank* r, void*) {  // (hit lists are small)
+        return host_call(r, residues, residues_len, offsets, lens, ids, n, pr, out, cigar,
+                         cigar_cap, cigar_used);
+      }))
+    return st;
+  if ((st = align_ready(b, pr.set)) != SW_OK) return st;
+  const size_t n_hits = pr.n_hits;
+  if (n_hits == 0) return SW_OK;
+  if (!offsets || !lens || (!pr.set && !pr.hits) || !out)
+    return fail(b, SW_ERR_ARG, "null host buffer");
+  if ((st = check_pairs(b, pr, n)) != SW_OK) return st;
+  Gathered g;
+  if ((st = gather_hits(b, residues, residues_len, offsets, lens, n, pr, g)) != SW_OK) return st;
+  HIPOK(b, hipSetDevice(b->device));
+  hipStream_t hs = b->stream;
+  SwkAlign p{};
+  if ((st = stage_hits(b, pr, g, p, hs)) != SW_OK) return st;
+  // passes A and B, the records back
+  if ((st = timed_on(b, hs, [&] { return swk_launch_align_ends(&p, hs); })) != SW_OK) return st;
   HIPOK(b, hipMemcpyAsync(out, b->al_out.p, n_hits * sizeof(sw_alignment), hipMemcpyDeviceToHost,
                           hs));
   HIPOK(b, hipStreamSynchronize(hs));
   size_t chunks = 0;
-  std::vector<uint32_t> ops;
   cigar_cap = std::min<size_t>(cigar_cap, 0xFFFFFFFFu);  // (cigar_offset is 32 bits)
-  if (cigar && cigar_cap) {
-    // the windows that fit the budget, in hit order, in chunks that fit it together; each hit's
-    // ops in a slot of rows + columns of the window (a path never has more ops)
-    const uint64_t budget = dir_budget();
-    std::vector<uint32_t> list;
-    std::vector<SwkAlignPlan> plan;
-    std::vector<size_t> cut{0};  // chunk c = positions [cut[c], cut[c + 1])
-    uint64_t used = 0, cig = 0, most = 0;
-    for (size_t h = 0; h < n_hits; ++h) {
-      const sw_alignment& r = out[h];
-      if (r.score <= 0) continue;
-      const uint32_t Q = r.q_end - r.q_start + 1, L = r.t_end - r.t_start + 1;
-      const uint64_t need = swk_align_dir_dwords(Q, L);
-      if (need > budget) continue;  // SW_ALIGN_NO_PATH, coordinates stay
-      if (used + need > budget) {
-        cut.push_back(list.size());
-        used = 0;
-      }
-      list.push_back((uint32_t)h);
-      plan.push_back(SwkAlignPlan{used, need, cig, Q + L, 0});
-      used += need;
-      most = std::max(most, used);
-      cig += (uint64_t)Q + L;
-    }
-    cut.push_back(list.size());
-    if (!list.empty()) {
-      HIPOK(b, b->al_dirs.reserve((size_t)most));
-      HIPOK(b, b->al_cig.reserve((size_t)cig));
-      HIPOK(b, b->al_list.reserve(list.size()));
-      HIPOK(b, b->al_plan.reserve(plan.size()));
-      HIPOK(b, hipMemcpyAsync(b->al_list.p, list.data(), list.size() * 4, hipMemcpyHostToDevice,
-                              hs));
-      HIPOK(b, hipMemcpyAsync(b->al_plan.p, plan.data(), plan.size() * sizeof(SwkAlignPlan),
+  const bool with_cigar = cigar && cigar_cap;
+  if (with_cigar) {
+    const Windows w = plan_windows(out, n_hits, dir_budget());
+    std::vector<uint32_t> ops;
+    if (!w.list.empty()) {  // passes C and D chunk by chunk, the records and the ops back
+      HIPOK(b, b->al_dirs.reserve((size_t)w.most));
+      HIPOK(b, b->al_cig.reserve((size_t)w.cig));
+      HIPOK(b, b->al_list.reserve(w.list.size()));
+      HIPOK(b, b->al_plan.reserve(w.plan.size()));
+      HIPOK(b, hipMemcpyAsync(b->al_list.p, w.list.data(), w.list.size() * 4,
+                              hipMemcpyHostToDevice, hs));
+      HIPOK(b, hipMemcpyAsync(b->al_plan.p, w.plan.data(), w.plan.size() * sizeof(SwkAlignPlan),
                               hipMemcpyHostToDevice, hs));
       p.cigar = b->al_cig.p;
       p.cigar_stride = 1;  // (places come from the plan)
-      Timed cd{b, hs};
-      if ((st = cd.begin()) != SW_OK) return st;
-      for (size_t c = 0; c + 1 < cut.size(); ++c) {
-        if (cut[c + 1] == cut[c]) continue;
-        HIPOK(b, swk_launch_align_paths(&p, b->al_list.p + cut[c], 0, cut[c + 1] - cut[c],
-                                        b->al_plan.p + cut[c], 0, b->al_dirs.p, hs));
-        ++chunks;
-      }
-      if ((st = cd.end()) != SW_OK) return st;
-      ops.resize((size_t)cig);
+      st = timed_on(b, hs, [&] {
+        for (size_t c = 0; c + 1 < w.cut.size(); ++c) {
+          if (w.cut[c + 1] == w.cut[c]) continue;
+          const hipError_t e =
+              swk_launch_align_paths(&p, b->al_list.p + w.cut[c], 0, w.cut[c + 1] - w.cut[c],
+                                     b->al_plan.p + w.cut[c], 0, b->al_dirs.p, hs);
+          if (e != hipSuccess) return e;
+          ++chunks;
+        }
+        return hipSuccess;
+      });
+      if (st != SW_OK) return st;
+      ops.resize((size_t)w.cig);
       HIPOK(b, hipMemcpyAsync(out, b->al_out.p, n_hits * sizeof(sw_alignment),
                               hipMemcpyDeviceToHost, hs));
       HIPOK(b, hipMemcpyAsync(ops.data(), b->al_cig.p, ops.size() * 4, hipMemcpyDeviceToHost, hs));
       HIPOK(b, hipStreamSynchronize(hs));
     }
-    // pack the ops back to back in hit order
-    size_t at = 0, k = 0;
-    for (size_t h = 0; h < n_hits; ++h) {
-      sw_alignment& r = out[h];
-      const bool planned = k < list.size() && list[k] == h;
-      const uint64_t from = planned ? plan[k].cig_off : 0;
-      if (planned) ++k;
-      r.cigar_offset = 0;
-      if (r.flags != 0 || !planned) continue;
-      if (r.cigar_len > cigar_cap - at) {
-        r.flags = SW_ALIGN_NO_PATH;
-        r.cigar_len = r.n_columns = r.n_identities = 0;
-        continue;
-      }
-      std::memcpy(cigar + at, ops.data() + from, (size_t)r.cigar_len * 4);
-      r.cigar_offset = (uint32_t)at;
-      at += r.cigar_len;
-    }
-    if (cigar_used) *cigar_used = at;
+    const size_t used = pack_ops(w, ops, out, n_hits, cigar, cigar_cap);
+    if (cigar_used) *cigar_used = used;
   }
   HIPOK(b, hipEventRecord(b->ev_used, hs));
-  for (size_t h = 0; h < n_hits; ++h) {  // the records speak of the caller's batch
-    if (!(cigar && cigar_cap)) out[h].cigar_offset = 0;
-    if (out[h].flags & SW_ALIGN_NO_HIT) continue;  // (index = id = SW_HIT_NONE)
-    const uint64_t t = target_of(h);
-    out[h].index = t;
-    out[h].id = ids ? ids[t] : t;
-    if (pr.strands && gs[h]) {  // the reverse strand: coordinates on the forward target
-      out[h].flags |= SW_ALIGN_REVERSE;
-      if (out[h].score > 0) {
-        const uint32_t ts = out[h].t_start, te = out[h].t_end;
-        out[h].t_start = glens[h] - 1 - te;
-        out[h].t_end = glens[h] - 1 - ts;
-      }
-    }
-  }
+  rewrite_records(pr, g, ids, with_cigar, out);
   name_kernel(b, pr.set, n_hits, chunks, pr.strand_call);
   return SW_OK;
 }

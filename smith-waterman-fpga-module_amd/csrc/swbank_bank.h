@@ -8,6 +8,11 @@
 // every row of a score matrix, the best query of every column), swbank_stat.hip (hit
 // statistics: the seeded shuffle, the score histogram, the estimate, bits and E-values),
 // swbank_strand.hip (both DNA strands: the reverse complement, the strand-merged scores).
+//
+// This header also holds what those units share: the buffer types, which free themselves with
+// the bank (DevBuf, UcBuf, PinBuf), the sliced scratch and the staged host batch (SliceScratch,
+// StagedBatch), and the scaffolding of an entry that runs after scoring (root_of, on_root,
+// stream_or, timed_on, scratch_event, slice_plan / slice_reserve, stage_host_batch).
 #ifndef SWBANK_BANK_H
 #define SWBANK_BANK_H
 
@@ -178,78 +183,104 @@ inline bool poison_buffers() {  // (read at every allocation: tests switch it pe
   return v && v[0] == '1';
 }
 
-template <typename T>
-struct DevBuf {
+// Buffers a bank holds at this moment, over all banks of the process: counted where a reserve
+// obtains memory and where memory is freed (a test hook, DESIGN §5: device-memory accounting is
+// far too coarse to show a leaked 64-element buffer).
+inline std::atomic<long> g_live_buffers{0};
+extern "C" long swbank_live_buffers(void);
+
+// What the three buffer types share: one owner (never copied), freed with it -- sw_bank_destroy
+// deletes the bank on its device, everything synchronised -- and counted while it holds memory.
+template <typename T, bool HOST>
+struct OwnedBuf {
   T* p = nullptr;
-  size_t cap = 0;  // elements
-  hipError_t reserve(size_t n) {
-    if (n <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
+  size_t cap = 0;  // elements (DevBuf) or bytes
+  OwnedBuf() = default;
+  OwnedBuf(const OwnedBuf&) = delete;
+  OwnedBuf& operator=(const OwnedBuf&) = delete;
+  ~OwnedBuf() { release(); }
+  void release() {
+    if (p) {
+      (void)(HOST ? hipHostFree(p) : hipFree(p));
+      g_live_buffers.fetch_sub(1, std::memory_order_relaxed);
+    }
     p = nullptr;
     cap = 0;
-    size_t want = std::max<size_t>(n, 64);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), want * sizeof(T));
-    if (e == hipSuccess) cap = want;
+  }
+
+ protected:
+  template <class A>
+  hipError_t obtain(size_t want, A&& alloc) {  // a reserve past cap: frees, then alloc(&p)
+    release();
+    const hipError_t e = alloc(reinterpret_cast<void**>(&p));
+    if (e != hipSuccess) {
+      p = nullptr;
+      return e;
+    }
+    cap = want;
+    g_live_buffers.fetch_add(1, std::memory_order_relaxed);
+    return e;
+  }
+};
+
+template <typename T>
+struct DevBuf : OwnedBuf<T, false> {
+  hipError_t reserve(size_t n) {
+    if (n <= this->cap) return hipSuccess;
+    const size_t want = std::max<size_t>(n, 64);
+    hipError_t e = this->obtain(want, [&](void** q) { return hipMalloc(q, want * sizeof(T)); });
     // (tests) SWBANK_POISON=1: new device buffers start as 0x3C bytes (f16 1.0 in every half)
     // instead of whatever the allocator hands back, so a read of a word nobody wrote shows;
     // complete before any bank stream uses the buffer
     if (e == hipSuccess && poison_buffers()) {
-      e = hipMemset(p, 0x3C, want * sizeof(T));
+      e = hipMemset(this->p, 0x3C, want * sizeof(T));
       if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     }
     return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
   }
 };
 
 // Device memory the caches do not keep (hipDeviceMallocUncached): a streamed batch's codes land
 // there by DMA while the kernel that reads them runs, so no cache line can be stale.
-struct UcBuf {
-  uint8_t* p = nullptr;
-  size_t cap = 0;  // bytes
+struct UcBuf : OwnedBuf<uint8_t, false> {
   hipError_t reserve(size_t n) {
     if (n <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    hipError_t e = hipExtMallocWithFlags(reinterpret_cast<void**>(&p), n, hipDeviceMallocUncached);
-    if (e == hipSuccess) cap = n;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
+    return obtain(n, [&](void** q) {
+      return hipExtMallocWithFlags(q, n, hipDeviceMallocUncached);
+    });
   }
 };
 
 // Pinned host staging for the query tables (so their uploads are truly asynchronous).
 // `flags`: hipHostMallocCoherent for words a running kernel reads (streamed chunk records).
-struct PinBuf {
-  unsigned flags = hipHostMallocDefault;
-  uint8_t* p = nullptr;
-  size_t cap = 0;  // bytes
+struct PinBuf : OwnedBuf<uint8_t, true> {
+  unsigned flags;
+  PinBuf(unsigned f = hipHostMallocDefault) : flags(f) {}
   hipError_t reserve(size_t n) {
     if (n <= cap) return hipSuccess;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
     const size_t want = std::max<size_t>(n, 4096);
-    hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&p), want, flags);
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
+    return obtain(want, [&](void** q) { return hipHostMalloc(q, want, flags); });
   }
 };
 
+// The sliced scratch of a call that scores a derived copy of the batch (its shuffle, its reverse
+// complement) slice by slice: the slice's codes at a fixed stride, an offset per target, nq rows
+// of scores (slice_plan, slice_reserve).
+struct SliceScratch {
+  DevBuf<uint8_t> codes;
+  DevBuf<uint64_t> offs;
+  DevBuf<int32_t> scores;
+};
+struct SlicePlan {
+  size_t stride, span, slices;  // bytes per target (0: no codes), targets per slice, slices
+};
+
+// A host batch staged on the root device for the device form of its call (stage_host_batch).
+struct StagedBatch {
+  DevBuf<uint8_t> res;
+  DevBuf<uint64_t> offs;
+  DevBuf<uint32_t> lens;
+};
 
 // Host worker threads for the host-buffer feeder (gather / scatter of a chunk): run(f) calls
 // f(part) for part = 0..size()-1, part 0 on the calling thread, and returns when all are done.
@@ -475,26 +506,27 @@ struct sw_bank {
   DevBuf<uint64_t> top_hits;
   DevBuf<uint32_t> top_cnt;
   hipEvent_t ev_top = nullptr;
-  // hit statistics (swbank_stat.hip): the estimate's shuffled codes, their offsets, the scores
-  // and the histogram rows (the call synchronises, so nothing outlives it); the host form's
-  // batch on the device; the significance call's per-row parameters, whose next upload waits
-  // for ev_stat (recorded after the kernel that reads them, on whichever stream it ran)
-  DevBuf<uint8_t> stat_codes, stat_hres;
-  DevBuf<uint64_t> stat_offs, stat_hoffs;
-  DevBuf<uint32_t> stat_hlens;
-  DevBuf<int32_t> stat_scores;
+  // hit statistics (swbank_stat.hip): the estimate's slices of shuffled codes, their offsets
+  // and scores (stat_slice) and the histogram rows (the call synchronises, so nothing outlives
+  // it); the host form's batch on the device (stat_host); the significance call's per-row
+  // parameters, whose next upload waits for ev_stat (recorded after the kernel that reads them,
+  // on whichever stream it ran)
+  SliceScratch stat_slice;
+  StagedBatch stat_host;
   DevBuf<unsigned long long> stat_cnt;
   DevBuf<double> stat_par;
   std::vector<double> stat_hpar;  // (the upload's source, kept until ev_stat)
   hipEvent_t ev_stat = nullptr;
   // both strands (swbank_strand.hip): the reverse complement of a slice of targets at a fixed
-  // stride, its offsets, the slice's reverse-strand scores; the host forms' batch, merged scores
-  // and strands on the device; ev_strand follows the last call's use of them, on whichever
-  // stream it ran, and the next call's stream waits for it
-  DevBuf<uint8_t> str_codes, str_hres, str_hstr;
-  DevBuf<uint64_t> str_offs, str_hoffs;
-  DevBuf<uint32_t> str_hlens;
-  DevBuf<int32_t> str_scores, str_hsc;
+  // stride, its offsets, the slice's reverse-strand scores (str_slice); the host forms' batch
+  // (str_host), merged scores and strands on the device; ev_strand follows the last call's use
+  // of them, on whichever stream it ran, and the next call's stream waits for it.  The two
+  // slice scratches and the two staged batches stay apart: a statistics call on one stream and a
+  // strand call on another are independent
+  SliceScratch str_slice;
+  StagedBatch str_host;
+  DevBuf<uint8_t> str_hstr;
+  DevBuf<int32_t> str_hsc;
   hipEvent_t ev_strand = nullptr;
   struct Seg { int W; size_t off, off16; };  // rows = W*R (last may be shorter); word offsets
                                               // in qtab and qtab16
@@ -702,6 +734,80 @@ struct Timed {  // one bracketed launch group (sw_bank_set_timing)
     ev = {};
   }
 };
+
+// One launch group on `hs`, bracketed for sw_bank_set_timing: f() launches and returns the
+// first HIP error; a group that fails keeps no events.
+template <class F>
+sw_status timed_on(sw_bank* b, hipStream_t hs, F&& f) {
+  Timed t{b, hs};
+  sw_status st = t.begin();
+  if (st != SW_OK) {
+    t.drop();
+    return st;
+  }
+  const hipError_t e = f();
+  if (e != hipSuccess) {
+    t.drop();
+    HIPOK(b, e);
+  }
+  if ((st = t.end()) != SW_OK) t.drop();
+  return st;
+}
+
+// ---- what the entries after scoring share -----------------------------
+// The bank whose device, stream and scratch a call uses: the root of a multi-device bank.
+inline sw_bank* root_of(sw_bank* b) { return b->is_multi() ? b->kids[0] : b; }
+
+// The caller's stream, or the bank's own for the ABI's NULL.
+inline hipStream_t stream_or(const sw_bank* b, void* stream) {
+  return stream ? reinterpret_cast<hipStream_t>(stream) : b->stream;
+}
+
+// A multi-device bank hands the call to its root, where the multi-device calls leave the
+// scores: call(root, the caller's stream or the root's), the root's failure text behind
+// "device N: " or its last_kernel becoming the bank's.  False on a single bank (nothing done);
+// else the call is over and `st` is its status.
+inline sw_status root_failed(sw_bank* b, const sw_bank* r, sw_status st) {
+  return fail(b, st, "device %d: %s", r->device, r->err);
+}
+template <class F>
+bool on_root(sw_bank* b, void* stream, sw_status& st, F&& call) {
+  if (!b->is_multi()) return false;
+  sw_bank* r = b->kids[0];
+  st = call(r, stream ? stream : static_cast<void*>(r->stream));
+  if (st != SW_OK)
+    st = root_failed(b, r, st);
+  else
+    snprintf(b->last_kernel, sizeof(b->last_kernel), "%s", r->last_kernel);
+  return true;
+}
+
+// The event that follows the last use of a scratch, on whichever stream that ran: created on
+// first use, otherwise `hs` waits for it.  The caller records it after what it launches.
+inline sw_status scratch_event(sw_bank* b, hipEvent_t& ev, hipStream_t hs) {
+  if (!ev)
+    HIPOK(b, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  else
+    HIPOK(b, hipStreamWaitEvent(hs, ev, 0));
+  return SW_OK;
+}
+
+// The slices of a call over n targets of at most max_len codes against nq queries: `codes`
+// when the slice holds codes of its own (at stride round16(max_len) + 16, with an offset per
+// target), the budget in MiB from the environment variable `budget_env` (default 256).
+sw_status slice_plan(sw_bank* b, const char* budget_env, size_t n, size_t nq, uint32_t max_len,
+                     bool codes, SlicePlan& plan);
+// Reserves `s` for a slice of the plan; the codes' padding is zeroed (on `hs`) when they grow.
+sw_status slice_reserve(sw_bank* b, SliceScratch& s, const SlicePlan& plan, size_t nq,
+                        hipStream_t hs);
+// Stages a host batch in `s` (of the root) on the root's stream: every target lies inside the
+// residues (`coded`: and, for the entry of that name, holds codes of the alphabet only), lo / hi
+// the shortest and longest length; then, on the root's device, the stream waits for `after` (if
+// any), the buffers are reserved (`zero`: and zeroed) and the uploads queued.
+sw_status stage_host_batch(sw_bank* b, StagedBatch& s, const uint8_t* residues,
+                           size_t residues_len, const uint64_t* offsets, const uint32_t* lens,
+                           size_t n, const char* coded, bool zero, hipEvent_t after, uint32_t& lo,
+                           uint32_t& hi);
 
 // RCCL for the multi-device score gather (SURVEY §8 e), loaded on first use (swbank_multi.hip).
 struct Rccl {

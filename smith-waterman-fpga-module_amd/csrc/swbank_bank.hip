@@ -150,6 +150,8 @@ extern "C" sw_status sw_bank_create(sw_bank** out, const sw_config* cfg_in) {
   return SW_OK;
 }
 
+// Every buffer of the bank frees itself when the bank is deleted: on the bank's device, after
+// everything that may still use one has been waited for.
 extern "C" void sw_bank_destroy(sw_bank* b) {
   DevGuard dev_guard(b);  // on the bank's device; the caller's is restored on return (ABI 6)
   if (!b) return;
@@ -164,13 +166,6 @@ extern "C" void sw_bank_destroy(sw_bank* b) {
     b->dpool.reset();
     b->pool.reset();
     (void)hipSetDevice(b->device);
-    b->grecv.release();
-    b->hrecv.release();
-    b->res.release();  // the device-call deal's staging (multi_device)
-    b->offs.release();
-    b->lens.release();
-    b->dperm.release();
-    b->dsort.release();
     delete b;
     return;
   }
@@ -182,16 +177,6 @@ extern "C" void sw_bank_destroy(sw_bank* b) {
   uint64_t nl;
   double pm, sm;
   (void)sw_bank_timing(b, &nl, &pm, &sm);
-  b->faultw.release();
-  b->qtab.release();
-  b->qtab16.release();
-  b->mqtab.release();
-  b->mqtab16.release();
-  b->mqpair.release();
-  b->qpair.release();
-  b->qpair_skew.release();
-  b->skew_ctab.release();
-  b->stage.release();
   if (b->ev_ready) (void)hipEventDestroy(b->ev_ready);
   if (b->ev_used) (void)hipEventDestroy(b->ev_used);
   if (b->best_ev) (void)hipEventDestroy(b->best_ev);
@@ -200,101 +185,89 @@ extern "C" void sw_bank_destroy(sw_bank* b) {
   if (b->ev_strand) (void)hipEventDestroy(b->ev_strand);
   if (b->ev_join) (void)hipEventDestroy(b->ev_join);
   for (hipEvent_t e : b->deal_ev) (void)hipEventDestroy(e);
-  b->fb_idx.release();
-  b->fb_cnt.release();
-  b->best_key.release();
-  b->best_dev.release();
-  b->i32prof.release();
-  b->i32scr.release();
-  b->al_tab.release();
-  b->al_res.release();
-  b->al_scr.release();
-  b->al_dirs.release();
-  b->al_lens.release();
-  b->al_cig.release();
-  b->al_list.release();
-  b->al_hq.release();
-  b->al_hs.release();
-  b->al_offs.release();
-  b->al_out.release();
-  b->al_plan.release();
-  b->top_state.release();
-  b->top_keys.release();
-  b->top_scores.release();
-  b->top_hsc.release();
-  b->top_hits.release();
-  b->top_cnt.release();
-  b->stat_codes.release();
-  b->stat_hres.release();
-  b->stat_offs.release();
-  b->stat_hoffs.release();
-  b->stat_hlens.release();
-  b->stat_scores.release();
-  b->stat_cnt.release();
-  b->stat_par.release();
-  b->str_codes.release();
-  b->str_hres.release();
-  b->str_hstr.release();
-  b->str_offs.release();
-  b->str_hoffs.release();
-  b->str_hlens.release();
-  b->str_scores.release();
-  b->str_hsc.release();
-  b->dperm.release();
-  b->dsort.release();
-  b->bal_state.release();
-  b->bal_flag.release();
-  b->wbal_state.release();
-  b->wbal_flag.release();
-  b->bal_plan.release();
-  b->wtab.release();
-  b->wtab16.release();
-  b->tprog.release();
-  for (int i = 0; i < 3; ++i) {
-    b->stab[i].release();
-    b->stab16[i].release();
-  }
-  b->sring.release();
-  b->edge[0].release();
-  b->edge[1].release();
   if (b->copy_stream) (void)hipStreamSynchronize(b->copy_stream);
   if (b->out_stream) (void)hipStreamSynchronize(b->out_stream);
   if (b->stream2) (void)hipStreamSynchronize(b->stream2);
   for (hipEvent_t e : b->out_ev) (void)hipEventDestroy(e);
-  for (int i = 0; i < sw_bank::NSLOT; ++i) b->hslot[i].release();
-  for (int i = 0; i < sw_bank::NDSLOT; ++i) {
-    b->dslot[i].release();
-    b->sortscr[i].release();
-  }
-  b->sbuf.release();
-  b->sflag.release();
-  b->sdrec.release();
-  b->sctr.release();
-  b->srec.release();
-  b->shflag.release();
-  b->shscores.release();
   for (hipEvent_t e : b->sev) (void)hipEventDestroy(e);
   for (int i = 0; i < sw_bank::NSLOT; ++i)
     if (b->h2d_done[i]) (void)hipEventDestroy(b->h2d_done[i]);
   for (int i = 0; i < sw_bank::NDSLOT; ++i)
     if (b->kern_done[i]) (void)hipEventDestroy(b->kern_done[i]);
-  b->hscores.release();
-  b->launcher.reset();
+  b->launcher.reset();  // (its thread and the pool's touch the pinned slots: gone before those)
   b->pool.reset();
   if (b->copy_stream) (void)hipStreamDestroy(b->copy_stream);
   if (b->out_stream) (void)hipStreamDestroy(b->out_stream);
   if (b->stream2) (void)hipStreamDestroy(b->stream2);
   if (b->kstream) (void)hipStreamDestroy(b->kstream);
   if (b->ev_s2) (void)hipEventDestroy(b->ev_s2);
-  b->res.release();
-  b->offs.release();
-  b->lens.release();
-  b->scores.release();
-  b->gres.release();
-  b->goffs.release();
-  b->glens.release();
   if (b->stream) (void)hipStreamDestroy(b->stream);
   delete b;
+}
+
+extern "C" long swbank_live_buffers(void) {
+  return g_live_buffers.load(std::memory_order_relaxed);
+}
+
+// ---- what the entries after scoring share (swbank_bank.h) ----------------------------------
+sw_status slice_plan(sw_bank* b, const char* budget_env, size_t n, size_t nq, uint32_t max_len,
+                     bool codes, SlicePlan& plan) {
+  plan.stride = codes ? ((size_t)max_len + 15) / 16 * 16 + 16 : 0;
+  if (plan.stride > UINT32_MAX) return fail(b, SW_ERR_ARG, "max_len %u too long", max_len);
+  const size_t per = nq * sizeof(int32_t) + (codes ? plan.stride + sizeof(uint64_t) : 0);
+  const size_t budget = (size_t)std::max(1, env_int(budget_env, 256)) << 20;
+  plan.span = std::min(n, std::max<size_t>(1, budget / per));
+  plan.slices = (n + plan.span - 1) / plan.span;
+  return SW_OK;
+}
+
+sw_status slice_reserve(sw_bank* b, SliceScratch& s, const SlicePlan& plan, size_t nq,
+                        hipStream_t hs) {
+  if (plan.stride) {
+    // (the stride's padding is never written: zeroed once, so whatever a score kernel reads past
+    // a target's end is a code of the alphabet, as in a caller's packed batch)
+    if (s.codes.cap < plan.span * plan.stride + 64) {
+      HIPOK(b, s.codes.reserve(plan.span * plan.stride + 64));
+      HIPOK(b, hipMemsetAsync(s.codes.p, 0, s.codes.cap, hs));
+    }
+    HIPOK(b, s.offs.reserve(plan.span));
+  }
+  HIPOK(b, s.scores.reserve(plan.span * nq));
+  return SW_OK;
+}
+
+sw_status stage_host_batch(sw_bank* b, StagedBatch& s, const uint8_t* residues,
+                           size_t residues_len, const uint64_t* offsets, const uint32_t* lens,
+                           size_t n, const char* coded, bool zero, hipEvent_t after, uint32_t& lo,
+                           uint32_t& hi) {
+  lo = UINT32_MAX;
+  hi = 0;
+  for (size_t k = 0; k < n; ++k) {
+    if (offsets[k] > residues_len || lens[k] > residues_len - offsets[k])
+      return fail(b, SW_ERR_ARG, "target %zu lies outside the %zu residues", k, residues_len);
+    if (coded) {
+      if (lens[k] && !residues) return fail(b, SW_ERR_ARG, "%s: null residues", coded);
+      for (uint32_t i = 0; i < lens[k]; ++i)
+        if (residues[offsets[k] + i] >= (uint32_t)b->alpha)
+          return fail(b, SW_ERR_ARG, "target %zu code %u at %u outside the alphabet", k,
+                      residues[offsets[k] + i], i);
+    }
+    lo = std::min(lo, lens[k]);
+    hi = std::max(hi, lens[k]);
+  }
+  sw_bank* r = root_of(b);
+  HIPOK(b, hipSetDevice(r->device));
+  hipStream_t hs = r->stream;
+  if (after) HIPOK(b, hipStreamWaitEvent(hs, after, 0));
+  HIPOK(b, s.res.reserve(residues_len + 64));
+  HIPOK(b, s.offs.reserve(n));
+  HIPOK(b, s.lens.reserve(n));
+  if (zero) HIPOK(b, hipMemsetAsync(s.res.p, 0, s.res.cap, hs));
+  if (residues_len)
+    HIPOK(b, hipMemcpyAsync(s.res.p, residues, residues_len, hipMemcpyHostToDevice, hs));
+  HIPOK(b, hipMemcpyAsync(s.offs.p, offsets, n * sizeof(uint64_t), hipMemcpyHostToDevice, hs));
+  HIPOK(b, hipMemcpyAsync(s.lens.p, lens, n * sizeof(uint32_t), hipMemcpyHostToDevice, hs));
+  return SW_OK;
 }
 
 extern "C" int32_t sw_bank_devices(const sw_bank* b, int32_t* devices, int32_t cap) {

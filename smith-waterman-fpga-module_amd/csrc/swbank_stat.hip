@@ -7,27 +7,6 @@
 
 namespace {
 
-// The bank whose device, stream and scratch a call uses: the root of a multi-device bank.
-sw_bank* root_of(sw_bank* b) { return b->is_multi() ? b->kids[0] : b; }
-
-// One launch group on `hs`, bracketed for sw_bank_set_timing like its siblings' (swbank_top.hip).
-template <class F>
-sw_status timed_on(sw_bank* b, hipStream_t hs, F&& f) {
-  Timed t{b, hs};
-  sw_status st = t.begin();
-  if (st != SW_OK) {
-    t.drop();
-    return st;
-  }
-  const hipError_t e = f();
-  if (e != hipSuccess) {
-    t.drop();
-    HIPOK(b, e);
-  }
-  if ((st = t.end()) != SW_OK) t.drop();
-  return st;
-}
-
 const char* bad_hist_args(const void* scores, const void* counts, size_t n, size_t nq) {
   if (!scores || !counts) return "null scores or counts";
   if (n == 0 || nq == 0) return "n and nq must be positive";
@@ -53,17 +32,13 @@ extern "C" sw_status sw_shuffle_batch_device(sw_bank* b, const uint8_t* d_res,
     return fail(b, SW_ERR_ARG, "sw_shuffle_batch_device: null device buffer");
   if (n == 0 || n >= 0x100000000ull)
     return fail(b, SW_ERR_ARG, "sw_shuffle_batch_device: 0 < n < 2^32");
-  if (b->is_multi()) {  // on the root device
-    sw_bank* r = b->kids[0];
-    const sw_status st = sw_shuffle_batch_device(r, d_res, d_offs, d_lens, n, max_len, seed, d_out,
-                                                 stream ? stream : r->stream);
-    if (st != SW_OK) return fail(b, st, "device %d: %s", r->device, r->err);
-    snprintf(b->last_kernel, sizeof(b->last_kernel), "%s", r->last_kernel);
-    return SW_OK;
-  }
+  if (sw_status st; on_root(b, stream, st, [&](sw_bank* r, void* s) {
+        return sw_shuffle_batch_device(r, d_res, d_offs, d_lens, n, max_len, seed, d_out, s);
+      }))
+    return st;
   if (const sw_status fs = take_fault(b, 0); fs != SW_OK) return fs;
   HIPOK(b, hipSetDevice(b->device));
-  hipStream_t hs = stream ? reinterpret_cast<hipStream_t>(stream) : b->stream;
+  hipStream_t hs = stream_or(b, stream);
   const sw_status st = timed_on(b, hs, [&] {
     return swk_shuffle_batch(d_res, d_offs, d_lens, n, max_len, 0, seed, d_out, nullptr, 0, hs);
   });
@@ -80,18 +55,14 @@ extern "C" sw_status sw_score_histogram_device(sw_bank* b, const int32_t* d_scor
   if (!b) return SW_ERR_ARG;
   if (const char* why = bad_hist_args(d_scores, d_counts, n, nq))
     return fail(b, SW_ERR_ARG, "sw_score_histogram_device: %s", why);
-  if (b->is_multi()) {  // on the root device, where the multi-device calls leave the scores
-    sw_bank* r = b->kids[0];
-    const sw_status st = sw_score_histogram_device(r, d_scores, d_lens, n, nq, d_counts,
-                                                   d_len_sums, d_clamped,
-                                                   stream ? stream : r->stream);
-    if (st != SW_OK) return fail(b, st, "device %d: %s", r->device, r->err);
-    snprintf(b->last_kernel, sizeof(b->last_kernel), "%s", r->last_kernel);
-    return SW_OK;
-  }
+  if (sw_status st; on_root(b, stream, st, [&](sw_bank* r, void* s) {
+        return sw_score_histogram_device(r, d_scores, d_lens, n, nq, d_counts, d_len_sums,
+                                         d_clamped, s);
+      }))
+    return st;
   if (const sw_status fs = take_fault(b, 0); fs != SW_OK) return fs;
   HIPOK(b, hipSetDevice(b->device));
-  hipStream_t hs = stream ? reinterpret_cast<hipStream_t>(stream) : b->stream;
+  hipStream_t hs = stream_or(b, stream);
   const sw_status st = timed_on(b, hs, [&] {
     return swk_stat_hist(d_scores, d_lens, n, nq, reinterpret_cast<unsigned long long*>(d_counts),
                          reinterpret_cast<unsigned long long*>(d_len_sums),
@@ -121,23 +92,15 @@ extern "C" sw_status sw_estimate_statistics_device(sw_bank* b, const uint8_t* d_
   if (const sw_status fs = take_fault(b, 0); fs != SW_OK) return fs;
   const size_t nq = sw_query_count(b);
   HIPOK(b, hipSetDevice(r->device));
-  hipStream_t hs = stream ? reinterpret_cast<hipStream_t>(stream) : r->stream;
+  hipStream_t hs = stream_or(r, stream);
   // a slice of targets: its shuffled codes at a fixed stride, its offsets, nq rows of scores
-  const size_t stride = ((size_t)max_len + 15) / 16 * 16 + 16;
-  if (stride > UINT32_MAX) return fail(b, SW_ERR_ARG, "max_len %u too long", max_len);
-  const size_t per = stride + sizeof(uint64_t) + nq * sizeof(int32_t);
-  const size_t budget = (size_t)std::max(1, env_int("SWBANK_STAT_MB", 256)) << 20;
-  const size_t span = std::min(n, std::max<size_t>(1, budget / per));
-  const size_t slices = (n + span - 1) / span;
+  SlicePlan pl;
+  SliceScratch& sl = r->stat_slice;
+  sw_status ps = slice_plan(b, "SWBANK_STAT_MB", n, nq, max_len, true, pl);
+  if (ps == SW_OK) ps = slice_reserve(b, sl, pl, nq, hs);
+  if (ps != SW_OK) return ps;
+  const size_t span = pl.span;
   const size_t row = (size_t)SW_STAT_BINS, words = nq * (2 * row + 1);  // counts, sums, clamped
-  // (the stride's padding is never written: zeroed once, so whatever a score kernel reads past
-  // a target's end is a code of the alphabet, as in a caller's packed batch)
-  if (r->stat_codes.cap < span * stride + 64) {
-    HIPOK(b, r->stat_codes.reserve(span * stride + 64));
-    HIPOK(b, hipMemsetAsync(r->stat_codes.p, 0, r->stat_codes.cap, hs));
-  }
-  HIPOK(b, r->stat_offs.reserve(span));
-  HIPOK(b, r->stat_scores.reserve(span * nq));
   HIPOK(b, r->stat_cnt.reserve(words));
   unsigned long long* counts = r->stat_cnt.p;
   unsigned long long* sums = counts + nq * row;
@@ -147,16 +110,16 @@ extern "C" sw_status sw_estimate_statistics_device(sw_bank* b, const uint8_t* d_
     for (size_t k0 = 0; k0 < n; k0 += span) {
       const size_t nk = std::min(span, n - k0);
       HIPOK(b, swk_shuffle_batch(d_res, d_offs + k0, d_lens + k0, nk, max_len, k0, seed + rd,
-                                 r->stat_codes.p, r->stat_offs.p, (uint32_t)stride, hs));
+                                 sl.codes.p, sl.offs.p, (uint32_t)pl.stride, hs));
       const sw_status st =
-          sw_score_batch_device_range(b, r->stat_codes.p, r->stat_offs.p, d_lens + k0, nullptr, nk,
-                                      min_len, max_len, r->stat_scores.p, hs);
+          sw_score_batch_device_range(b, sl.codes.p, sl.offs.p, d_lens + k0, nullptr, nk, min_len,
+                                      max_len, sl.scores.p, hs);
       if (st != SW_OK) {
         (void)hipStreamSynchronize(hs);  // (nothing of the call is left in flight)
         return st;
       }
       HIPOK(b, hipSetDevice(r->device));
-      HIPOK(b, swk_stat_hist(r->stat_scores.p, d_lens + k0, nk, nq, counts, sums, clamped, hs));
+      HIPOK(b, swk_stat_hist(sl.scores.p, d_lens + k0, nk, nq, counts, sums, clamped, hs));
     }
   }
   std::vector<unsigned long long> host(words);
@@ -176,7 +139,7 @@ extern "C" sw_status sw_estimate_statistics_device(sw_bank* b, const uint8_t* d_
     if (out[i].n_clamped) out[i].flags |= SW_STAT_CLAMPED;
   }
   snprintf(b->last_kernel, sizeof(b->last_kernel), "stats rounds=%u nq=%zu n=%zu slices=%zu",
-           rounds, nq, n, slices);
+           rounds, nq, n, pl.slices);
   return SW_OK;
 }
 
@@ -193,26 +156,14 @@ extern "C" sw_status sw_estimate_statistics(sw_bank* b, const uint8_t* residues,
   sw_bank* r = root_of(b);
   if (!r->have_pen || !b->have_query)
     return fail(b, SW_ERR_STATE, "penalties or query not loaded");
-  uint32_t lo = UINT32_MAX, hi = 0;
-  for (size_t k = 0; k < n; ++k) {
-    if (offsets[k] > residues_len || lens[k] > residues_len - offsets[k])
-      return fail(b, SW_ERR_ARG, "target %zu lies outside the %zu residues", k, residues_len);
-    lo = std::min(lo, lens[k]);
-    hi = std::max(hi, lens[k]);
-  }
-  HIPOK(b, hipSetDevice(r->device));
+  uint32_t lo, hi;
+  StagedBatch& sb = r->stat_host;
+  sw_status st = stage_host_batch(b, sb, residues, residues_len, offsets, lens, n, nullptr, false,
+                                  nullptr, lo, hi);
+  if (st != SW_OK) return st;
   hipStream_t hs = r->stream;
-  HIPOK(b, r->stat_hres.reserve(residues_len + 64));
-  HIPOK(b, r->stat_hoffs.reserve(n));
-  HIPOK(b, r->stat_hlens.reserve(n));
-  if (residues_len)
-    HIPOK(b, hipMemcpyAsync(r->stat_hres.p, residues, residues_len, hipMemcpyHostToDevice, hs));
-  HIPOK(b, hipMemcpyAsync(r->stat_hoffs.p, offsets, n * sizeof(uint64_t), hipMemcpyHostToDevice,
-                          hs));
-  HIPOK(b, hipMemcpyAsync(r->stat_hlens.p, lens, n * sizeof(uint32_t), hipMemcpyHostToDevice, hs));
-  const sw_status st = sw_estimate_statistics_device(b, r->stat_hres.p, r->stat_hoffs.p,
-                                                     r->stat_hlens.p, n, lo, hi, seed, rounds, out,
-                                                     hs);
+  st = sw_estimate_statistics_device(b, sb.res.p, sb.offs.p, sb.lens.p, n, lo, hi, seed, rounds,
+                                     out, hs);
   if (st != SW_OK) (void)hipStreamSynchronize(hs);  // (the uploads have left the caller's buffers)
   return st;
 }
@@ -234,18 +185,14 @@ extern "C" sw_status sw_hit_significance_device(sw_bank* b, const sw_statistics*
   for (size_t i = 0; i < nq; ++i)
     if (degenerate(st[i]))
       return fail(b, SW_ERR_ARG, "sw_hit_significance_device: degenerate statistics (row %zu)", i);
-  if (b->is_multi()) {  // on the root device
-    sw_bank* r = b->kids[0];
-    const sw_status s = sw_hit_significance_device(r, st, d_hit_scores, d_hits, d_lens,
-                                                   hits_per_query, nq, db_size, d_bits, d_evalues,
-                                                   stream ? stream : r->stream);
-    if (s != SW_OK) return fail(b, s, "device %d: %s", r->device, r->err);
-    snprintf(b->last_kernel, sizeof(b->last_kernel), "%s", r->last_kernel);
-    return SW_OK;
-  }
+  if (sw_status fs; on_root(b, stream, fs, [&](sw_bank* r, void* s) {
+        return sw_hit_significance_device(r, st, d_hit_scores, d_hits, d_lens, hits_per_query, nq,
+                                          db_size, d_bits, d_evalues, s);
+      }))
+    return fs;
   if (const sw_status fs = take_fault(b, 0); fs != SW_OK) return fs;
   HIPOK(b, hipSetDevice(b->device));
-  hipStream_t hs = stream ? reinterpret_cast<hipStream_t>(stream) : b->stream;
+  hipStream_t hs = stream_or(b, stream);
   // the previous call's upload and kernel (on any stream) are done with the parameters, on the
   // host and on the device, before they are replaced: a short host wait for a small kernel
   if (!b->ev_stat) HIPOK(b, hipEventCreateWithFlags(&b->ev_stat, hipEventDisableTiming));

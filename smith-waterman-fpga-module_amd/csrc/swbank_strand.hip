@@ -8,27 +8,6 @@
 
 namespace {
 
-// The bank whose device, stream and scratch a call uses: the root of a multi-device bank.
-sw_bank* root_of(sw_bank* b) { return b->is_multi() ? b->kids[0] : b; }
-
-// One launch group on `hs`, bracketed for sw_bank_set_timing like its siblings' (swbank_stat.hip).
-template <class F>
-sw_status timed_on(sw_bank* b, hipStream_t hs, F&& f) {
-  Timed t{b, hs};
-  sw_status st = t.begin();
-  if (st != SW_OK) {
-    t.drop();
-    return st;
-  }
-  const hipError_t e = f();
-  if (e != hipSuccess) {
-    t.drop();
-    HIPOK(b, e);
-  }
-  if ((st = t.end()) != SW_OK) t.drop();
-  return st;
-}
-
 sw_status dna_only(sw_bank* b, const char* what) {
   if (b->cfg.alphabet != SW_ALPHABET_DNA)
     return fail(b, SW_ERR_UNSUPPORTED, "%s: DNA banks only (a protein has no reverse strand)", what);
@@ -47,17 +26,13 @@ extern "C" sw_status sw_revcomp_batch_device(sw_bank* b, const uint8_t* d_res,
     return fail(b, SW_ERR_ARG, "sw_revcomp_batch_device: null device buffer");
   if (n == 0 || n >= 0x100000000ull)
     return fail(b, SW_ERR_ARG, "sw_revcomp_batch_device: 0 < n < 2^32");
-  if (b->is_multi()) {  // on the root device
-    sw_bank* r = b->kids[0];
-    const sw_status st =
-        sw_revcomp_batch_device(r, d_res, d_offs, d_lens, n, d_out, stream ? stream : r->stream);
-    if (st != SW_OK) return fail(b, st, "device %d: %s", r->device, r->err);
-    snprintf(b->last_kernel, sizeof(b->last_kernel), "%s", r->last_kernel);
-    return SW_OK;
-  }
+  if (sw_status st; on_root(b, stream, st, [&](sw_bank* r, void* s) {
+        return sw_revcomp_batch_device(r, d_res, d_offs, d_lens, n, d_out, s);
+      }))
+    return st;
   if (const sw_status fs = take_fault(b, 0); fs != SW_OK) return fs;
   HIPOK(b, hipSetDevice(b->device));
-  hipStream_t hs = stream ? reinterpret_cast<hipStream_t>(stream) : b->stream;
+  hipStream_t hs = stream_or(b, stream);
   const sw_status st = timed_on(b, hs, [&] {
     return swk_revcomp_batch(d_res, d_offs, d_lens, n, d_out, nullptr, 0, hs);
   });
@@ -87,61 +62,50 @@ extern "C" sw_status sw_score_strands_device(sw_bank* b, const uint8_t* d_res, c
   if (n > SIZE_MAX / sizeof(int32_t) / nq)
     return fail(b, SW_ERR_ARG, "sw_score_strands_device: nq x n overflows size_t");
   HIPOK(b, hipSetDevice(r->device));
-  hipStream_t hs = stream ? reinterpret_cast<hipStream_t>(stream) : r->stream;
+  hipStream_t hs = stream_or(r, stream);
   // a slice of targets: its reverse-strand scores and, without the caller's d_rc, its reverse
   // complement at a fixed stride and the offsets of that
-  const size_t stride = d_rc ? 0 : ((size_t)max_len + 15) / 16 * 16 + 16;
-  if (stride > UINT32_MAX) return fail(b, SW_ERR_ARG, "max_len %u too long", max_len);
-  const size_t per = nq * sizeof(int32_t) + (d_rc ? 0 : stride + sizeof(uint64_t));
-  const size_t budget = (size_t)std::max(1, env_int("SWBANK_STRAND_MB", 256)) << 20;
-  const size_t span = std::min(n, std::max<size_t>(1, budget / per));
-  const size_t slices = (n + span - 1) / span;
+  SlicePlan pl;
+  SliceScratch& sl = r->str_slice;
+  sw_status st = slice_plan(b, "SWBANK_STRAND_MB", n, nq, max_len, !d_rc, pl);
+  if (st != SW_OK) return st;
+  const size_t span = pl.span;
   // the forward strand, the whole batch, straight into the caller's matrix
-  sw_status st =
-      sw_score_batch_device_range(b, d_res, d_offs, d_lens, nullptr, n, min_len, max_len, d_scores, hs);
+  st = sw_score_batch_device_range(b, d_res, d_offs, d_lens, nullptr, n, min_len, max_len, d_scores,
+                                   hs);
   if (st != SW_OK) return st;
   HIPOK(b, hipSetDevice(r->device));
   // the previous call's use of the scratch, on whichever stream it ran
-  if (!r->ev_strand) HIPOK(b, hipEventCreateWithFlags(&r->ev_strand, hipEventDisableTiming));
-  else HIPOK(b, hipStreamWaitEvent(hs, r->ev_strand, 0));
-  if (!d_rc) {
-    // (the stride's padding is never written: zeroed once, so whatever a score kernel reads past
-    // a target's end is a code of the alphabet, as in a caller's packed batch)
-    if (r->str_codes.cap < span * stride + 64) {
-      HIPOK(b, r->str_codes.reserve(span * stride + 64));
-      HIPOK(b, hipMemsetAsync(r->str_codes.p, 0, r->str_codes.cap, hs));
-    }
-    HIPOK(b, r->str_offs.reserve(span));
-  }
-  HIPOK(b, r->str_scores.reserve(span * nq));
+  if ((st = scratch_event(b, r->ev_strand, hs)) != SW_OK) return st;
+  if ((st = slice_reserve(b, sl, pl, nq, hs)) != SW_OK) return st;
   for (size_t k0 = 0; k0 < n && st == SW_OK; k0 += span) {
     const size_t nk = std::min(span, n - k0);
     const uint8_t* res = d_rc;
     const uint64_t* offs = d_offs + k0;
     if (!d_rc) {
       st = timed_on(b, hs, [&] {
-        return swk_revcomp_batch(d_res, d_offs + k0, d_lens + k0, nk, r->str_codes.p,
-                                 r->str_offs.p, (uint32_t)stride, hs);
+        return swk_revcomp_batch(d_res, d_offs + k0, d_lens + k0, nk, sl.codes.p, sl.offs.p,
+                                 (uint32_t)pl.stride, hs);
       });
       if (st != SW_OK) break;
-      res = r->str_codes.p;
-      offs = r->str_offs.p;
+      res = sl.codes.p;
+      offs = sl.offs.p;
     }
     st = sw_score_batch_device_range(b, res, offs, d_lens + k0, nullptr, nk, min_len, max_len,
-                                     r->str_scores.p, hs);
+                                     sl.scores.p, hs);
     if (st != SW_OK) break;
     HIPOK(b, hipSetDevice(r->device));
     st = timed_on(b, hs, [&] {
-      return swk_strand_merge(d_scores, r->str_scores.p, d_strands, n, k0, nk, nq, hs);
+      return swk_strand_merge(d_scores, sl.scores.p, d_strands, n, k0, nk, nq, hs);
     });
   }
   // whatever was launched uses the scratch: the next call is ordered after it in any case, and
   // sw_bank_sync waits for the merge
   const hipError_t er = hipEventRecord(r->ev_strand, hs);
-  if (st != SW_OK) return b == r ? st : fail(b, st, "device %d: %s", r->device, r->err);
+  if (st != SW_OK) return b == r ? st : root_failed(b, r, st);
   HIPOK(b, er);
   snprintf(b->last_kernel, sizeof(b->last_kernel), "strands nq=%zu n=%zu slices=%zu", nq, n,
-           slices);
+           pl.slices);
   return SW_OK;
 }
 
@@ -161,37 +125,23 @@ extern "C" sw_status sw_score_strands(sw_bank* b, const uint8_t* residues, size_
   const size_t nq = sw_query_count(b);
   if (n > SIZE_MAX / sizeof(int32_t) / nq)
     return fail(b, SW_ERR_ARG, "sw_score_strands: nq x n overflows size_t");
-  uint32_t lo = UINT32_MAX, hi = 0;
-  for (size_t k = 0; k < n; ++k) {
-    if (offsets[k] > residues_len || lens[k] > residues_len - offsets[k])
-      return fail(b, SW_ERR_ARG, "target %zu lies outside the %zu residues", k, residues_len);
-    if (lens[k] && !residues) return fail(b, SW_ERR_ARG, "sw_score_strands: null residues");
-    for (uint32_t i = 0; i < lens[k]; ++i)
-      if (residues[offsets[k] + i] >= (uint32_t)SW_DNA_ALPHA)
-        return fail(b, SW_ERR_ARG, "target %zu code %u at %u outside the alphabet", k,
-                    residues[offsets[k] + i], i);
-    lo = std::min(lo, lens[k]);
-    hi = std::max(hi, lens[k]);
-  }
-  HIPOK(b, hipSetDevice(r->device));
+  // the previous call (on any stream) is done with the buffers before they are refilled; the
+  // codes zeroed like a caller's padded batch: what a score kernel reads past the last target's
+  // end is a code of the alphabet
+  uint32_t lo, hi;
+  StagedBatch& sb = r->str_host;
+  sw_status st = stage_host_batch(b, sb, residues, residues_len, offsets, lens, n,
+                                  "sw_score_strands", true, r->ev_strand, lo, hi);
+  if (st != SW_OK) return st;
   hipStream_t hs = r->stream;
-  // the previous call (on any stream) is done with the buffers before they are refilled
-  if (r->ev_strand) HIPOK(b, hipStreamWaitEvent(hs, r->ev_strand, 0));
-  HIPOK(b, r->str_hres.reserve(residues_len + 64));
-  HIPOK(b, r->str_hoffs.reserve(n));
-  HIPOK(b, r->str_hlens.reserve(n));
-  HIPOK(b, r->str_hsc.reserve(nq * n));
-  if (strands_out) HIPOK(b, r->str_hstr.reserve(nq * n));
-  // (zeroed like a caller's padded batch: what a score kernel reads past the last target's end
-  // is a code of the alphabet)
-  HIPOK(b, hipMemsetAsync(r->str_hres.p, 0, r->str_hres.cap, hs));
-  if (residues_len)
-    HIPOK(b, hipMemcpyAsync(r->str_hres.p, residues, residues_len, hipMemcpyHostToDevice, hs));
-  HIPOK(b, hipMemcpyAsync(r->str_hoffs.p, offsets, n * sizeof(uint64_t), hipMemcpyHostToDevice, hs));
-  HIPOK(b, hipMemcpyAsync(r->str_hlens.p, lens, n * sizeof(uint32_t), hipMemcpyHostToDevice, hs));
-  sw_status st = sw_score_strands_device(b, r->str_hres.p, nullptr, r->str_hoffs.p, r->str_hlens.p,
-                                         n, lo, hi, r->str_hsc.p, strands_out ? r->str_hstr.p : nullptr,
-                                         hs);
+  hipError_t e = r->str_hsc.reserve(nq * n);
+  if (e == hipSuccess && strands_out) e = r->str_hstr.reserve(nq * n);
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(hs);  // (the uploads have left the caller's buffers)
+    HIPOK(b, e);
+  }
+  st = sw_score_strands_device(b, sb.res.p, nullptr, sb.offs.p, sb.lens.p, n, lo, hi, r->str_hsc.p,
+                               strands_out ? r->str_hstr.p : nullptr, hs);
   if (st != SW_OK) {
     (void)hipStreamSynchronize(hs);  // (the uploads have left the caller's buffers)
     return st;

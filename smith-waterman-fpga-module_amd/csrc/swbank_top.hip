@@ -23,27 +23,16 @@ sw_status select_on(sw_bank* b, const int32_t* d_scores, const uint64_t* d_ids, 
                     uint64_t* d_hit_ids, uint32_t* d_counts, hipStream_t hs) {
   HIPOK(b, b->top_state.reserve(nq * swk_top_state_words()));
   HIPOK(b, b->top_keys.reserve(nq * k));
-  if (!b->ev_top) HIPOK(b, hipEventCreateWithFlags(&b->ev_top, hipEventDisableTiming));
-  else HIPOK(b, hipStreamWaitEvent(hs, b->ev_top, 0));
-  Timed t{b, hs};
-  sw_status st = t.begin();
-  if (st != SW_OK) {
-    t.drop();
-    return st;
-  }
-  const hipError_t e = swk_top_hits(d_scores, d_ids, n, nq, k, min_score, b->top_state.p,
-                                    b->top_keys.p, d_hits, d_hit_scores, d_hit_ids, d_counts, hs);
-  // whatever was launched uses the scratch: the next call is ordered after it in any case
-  const hipError_t er = hipEventRecord(b->ev_top, hs);
-  if (e != hipSuccess || er != hipSuccess) {
-    t.drop();
-    HIPOK(b, e);
-    HIPOK(b, er);
-  }
-  if ((st = t.end()) != SW_OK) {
-    t.drop();
-    return st;
-  }
+  sw_status st = scratch_event(b, b->ev_top, hs);
+  if (st != SW_OK) return st;
+  st = timed_on(b, hs, [&] {
+    const hipError_t e = swk_top_hits(d_scores, d_ids, n, nq, k, min_score, b->top_state.p,
+                                      b->top_keys.p, d_hits, d_hit_scores, d_hit_ids, d_counts, hs);
+    // whatever was launched uses the scratch: the next call is ordered after it in any case
+    const hipError_t er = hipEventRecord(b->ev_top, hs);
+    return e != hipSuccess ? e : er;
+  });
+  if (st != SW_OK) return st;
   snprintf(b->last_kernel, sizeof(b->last_kernel), "top k=%zu nq=%zu n=%zu", k, nq, n);
   return SW_OK;
 }
@@ -65,26 +54,16 @@ sw_status best_queries_on(sw_bank* b, const int32_t* d_scores, size_t n, size_t 
                           hipStream_t hs) {
   const size_t nkeys = swk_best_queries_keys(n, nq);
   if (nkeys) HIPOK(b, b->top_keys.reserve(nkeys));
-  if (!b->ev_top) HIPOK(b, hipEventCreateWithFlags(&b->ev_top, hipEventDisableTiming));
-  else HIPOK(b, hipStreamWaitEvent(hs, b->ev_top, 0));
-  Timed t{b, hs};
-  sw_status st = t.begin();
-  if (st != SW_OK) {
-    t.drop();
-    return st;
-  }
-  const hipError_t e = swk_best_queries(d_scores, n, nq, min_score, nkeys ? b->top_keys.p : nullptr,
-                                        d_best_query, d_best_score, hs);
-  const hipError_t er = hipEventRecord(b->ev_top, hs);
-  if (e != hipSuccess || er != hipSuccess) {
-    t.drop();
-    HIPOK(b, e);
-    HIPOK(b, er);
-  }
-  if ((st = t.end()) != SW_OK) {
-    t.drop();
-    return st;
-  }
+  sw_status st = scratch_event(b, b->ev_top, hs);
+  if (st != SW_OK) return st;
+  st = timed_on(b, hs, [&] {
+    const hipError_t e = swk_best_queries(d_scores, n, nq, min_score,
+                                          nkeys ? b->top_keys.p : nullptr, d_best_query,
+                                          d_best_score, hs);
+    const hipError_t er = hipEventRecord(b->ev_top, hs);  // (as in select_on)
+    return e != hipSuccess ? e : er;
+  });
+  if (st != SW_OK) return st;
   snprintf(b->last_kernel, sizeof(b->last_kernel), "best-query nq=%zu n=%zu", nq, n);
   return SW_OK;
 }
@@ -98,19 +77,15 @@ extern "C" sw_status sw_best_queries_device(sw_bank* b, const int32_t* d_scores,
   if (!b) return SW_ERR_ARG;
   if (const char* why = bad_best_args(d_scores, d_best_query, d_best_score, n, nq))
     return fail(b, SW_ERR_ARG, "sw_best_queries_device: %s", why);
-  if (b->is_multi()) {  // on the root device, where the multi-device calls leave the scores
-    sw_bank* r = b->kids[0];
-    const sw_status st = sw_best_queries_device(r, d_scores, n, nq, min_score, d_best_query,
-                                                d_best_score, stream ? stream : r->stream);
-    if (st != SW_OK) return fail(b, st, "device %d: %s", r->device, r->err);
-    snprintf(b->last_kernel, sizeof(b->last_kernel), "%s", r->last_kernel);
-    return SW_OK;
-  }
+  if (sw_status st; on_root(b, stream, st, [&](sw_bank* r, void* s) {
+        return sw_best_queries_device(r, d_scores, n, nq, min_score, d_best_query, d_best_score, s);
+      }))
+    return st;
   // a hand-off fault latched by an earlier device call is returned before anything runs
   if (const sw_status fs = take_fault(b, 0); fs != SW_OK) return fs;
   HIPOK(b, hipSetDevice(b->device));
   return best_queries_on(b, d_scores, n, nq, min_score, d_best_query, d_best_score,
-                         stream ? reinterpret_cast<hipStream_t>(stream) : b->stream);
+                         stream_or(b, stream));
 }
 
 extern "C" sw_status sw_best_queries(sw_bank* b, const int32_t* scores, size_t n, size_t nq,
@@ -120,13 +95,10 @@ extern "C" sw_status sw_best_queries(sw_bank* b, const int32_t* scores, size_t n
   if (!b) return SW_ERR_ARG;
   if (const char* why = bad_best_args(scores, best_query, best_score, n, nq))
     return fail(b, SW_ERR_ARG, "sw_best_queries: %s", why);
-  if (b->is_multi()) {  // on the root device
-    sw_bank* r = b->kids[0];
-    const sw_status st = sw_best_queries(r, scores, n, nq, min_score, best_query, best_score);
-    if (st != SW_OK) return fail(b, st, "device %d: %s", r->device, r->err);
-    snprintf(b->last_kernel, sizeof(b->last_kernel), "%s", r->last_kernel);
-    return SW_OK;
-  }
+  if (sw_status st; on_root(b, nullptr, st, [&](sw_bank* r, void*) {
+        return sw_best_queries(r, scores, n, nq, min_score, best_query, best_score);
+      }))
+    return st;
   if (const sw_status fs = take_fault(b, 0); fs != SW_OK) return fs;
   HIPOK(b, hipSetDevice(b->device));
   hipStream_t hs = b->stream;
@@ -160,20 +132,16 @@ extern "C" sw_status sw_top_hits_device(sw_bank* b, const int32_t* d_scores, con
   if (!b) return SW_ERR_ARG;
   if (const char* why = bad_args(d_scores, d_hits, n, nq, k))
     return fail(b, SW_ERR_ARG, "sw_top_hits_device: %s", why);
-  if (b->is_multi()) {  // on the root device, where the multi-device calls leave the scores
-    sw_bank* r = b->kids[0];
-    const sw_status st = sw_top_hits_device(r, d_scores, d_ids, n, nq, k, min_score, d_hits,
-                                            d_hit_scores, d_hit_ids, d_counts,
-                                            stream ? stream : r->stream);
-    if (st != SW_OK) return fail(b, st, "device %d: %s", r->device, r->err);
-    snprintf(b->last_kernel, sizeof(b->last_kernel), "%s", r->last_kernel);
-    return SW_OK;
-  }
+  if (sw_status st; on_root(b, stream, st, [&](sw_bank* r, void* s) {
+        return sw_top_hits_device(r, d_scores, d_ids, n, nq, k, min_score, d_hits, d_hit_scores,
+                                  d_hit_ids, d_counts, s);
+      }))
+    return st;
   // a hand-off fault latched by an earlier device call is returned before anything runs
   if (const sw_status fs = take_fault(b, 0); fs != SW_OK) return fs;
   HIPOK(b, hipSetDevice(b->device));
   return select_on(b, d_scores, d_ids, n, nq, k, min_score, d_hits, d_hit_scores, d_hit_ids,
-                   d_counts, stream ? reinterpret_cast<hipStream_t>(stream) : b->stream);
+                   d_counts, stream_or(b, stream));
 }
 
 extern "C" sw_status sw_top_hits(sw_bank* b, const int32_t* scores, const uint64_t* ids, size_t n,
@@ -185,14 +153,10 @@ extern "C" sw_status sw_top_hits(sw_bank* b, const int32_t* scores, const uint64
     return fail(b, SW_ERR_ARG, "sw_top_hits: %s", why);
   if (nq > SIZE_MAX / sizeof(uint64_t) / std::max(n, k))
     return fail(b, SW_ERR_ARG, "sw_top_hits: nq x n or nq x k bytes overflow size_t");
-  if (b->is_multi()) {  // on the root device
-    sw_bank* r = b->kids[0];
-    const sw_status st =
-        sw_top_hits(r, scores, ids, n, nq, k, min_score, hits, hit_scores, hit_ids, counts);
-    if (st != SW_OK) return fail(b, st, "device %d: %s", r->device, r->err);
-    snprintf(b->last_kernel, sizeof(b->last_kernel), "%s", r->last_kernel);
-    return SW_OK;
-  }
+  if (sw_status st; on_root(b, nullptr, st, [&](sw_bank* r, void*) {
+        return sw_top_hits(r, scores, ids, n, nq, k, min_score, hits, hit_scores, hit_ids, counts);
+      }))
+    return st;
   HIPOK(b, hipSetDevice(b->device));
   hipStream_t hs = b->stream;
   // the previous call (on any stream) is done with the buffers before they are refilled
