@@ -89,7 +89,9 @@ extern "C" {
  *        sw_score_histogram_device, sw_fit_statistics, sw_estimate_statistics[_device],
  *        sw_hit_significance[_device], sw_statistics; (test SWBANK_HAS_STRANDS) both DNA
  *        strands -- sw_revcomp_codes, sw_revcomp_batch_device, sw_score_strands[_device],
- *        sw_align_strand_hits[_device], SW_ALIGN_REVERSE. */
+ *        sw_align_strand_hits[_device], SW_ALIGN_REVERSE; (test SWBANK_HAS_FRAMES) the
+ *        translated search -- sw_translate_codes, sw_translate_batch_device,
+ *        sw_score_frames[_device], sw_align_frame_hits[_device], SW_ALIGN_FRAME_SHIFT / _MASK. */
 #define SWBANK_ABI_VERSION 6
 #define SWBANK_HAS_ALIGN 1
 #define SWBANK_HAS_TOPK 1
@@ -725,6 +727,125 @@ sw_status sw_align_strand_hits(sw_bank *bank, const uint8_t *residues, size_t re
                                size_t hits_per_query, const uint64_t *hits, size_t n_hits,
                                sw_alignment *out, uint32_t *cigar, size_t cigar_cap,
                                size_t *cigar_used);
+
+/* ---- translated search: a protein query against DNA in six reading frames (ABI 6 addition) ----
+ * What the FASTA suite's tfastx does without frameshifts: every DNA target is translated in its
+ * three forward and three reverse reading frames, each frame is scored against the protein
+ * query with the bank's matrix, and the best frame is kept.
+ *
+ * Definitions:
+ *   codon     three adjacent DNA codes c0 c1 c2 (SW_DNA_T = 0, C = 1, A = 2, G = 3, N = 4).  All
+ *             three below 4: the amino acid is table[c0 * 16 + c1 * 4 + c2] -- the T,C,A,G order
+ *             of a genetic-code table, so the codes index it directly.  Any of the three at 4 or
+ *             above: X (protein code 22).  The default table is the standard code,
+ *             FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG, its letters as the
+ *             protein codes of ARNDCQEGHILKMFPSTWYVBZX*.  A stop is * (code 23): it stays in the
+ *             frame and is scored by the matrix like any residue; frames are not split at stops.
+ *             codon_table: 64 protein codes in host memory, NULL for the standard code; an entry
+ *             of 24 or more is SW_ERR_ARG.
+ *   frame f   of a target of L codes, f in 0..5.  Frames 0..2 are the forward frames: frame f is
+ *             codons j = 0 .. (L - f) / 3 - 1 over codes f + 3j .. f + 3j + 2, empty when
+ *             L < f + 3.  Frames 3..5 are frames 0..2 of rc(target), rc as sw_revcomp_codes.
+ *             The frame score of (query, target, f) is what the bank returns for (query, the
+ *             translation of frame f): exact by construction for every matrix and gap model.
+ *   merged    score = max over f; frame = the lowest f that reaches it.  A target with no codon
+ *             scores 0 in frame 0.
+ *   bank      protein banks only (SW_ALPHABET_PROTEIN): every call below returns
+ *             SW_ERR_UNSUPPORTED on a DNA bank.  The batch holds DNA byte codes 0..4: the host
+ *             forms return SW_ERR_ARG for a code of 5 or more, the device forms validate nothing
+ *             and translate such a code as X.
+ */
+#define SWBANK_HAS_FRAMES 1
+#define SW_FRAME_COUNT 6
+
+/* Host, no device: out[0..) = the translation of frame `frame` (0..5) of codes[0..n); returns
+ * the codons written (0 for a NULL codes or out, a frame above 5 or a table entry >= 24). */
+size_t sw_translate_codes(const uint8_t *codes, size_t n, uint32_t frame,
+                          const uint8_t *codon_table, uint8_t *out);
+
+/* Device buffers, asynchronous on `stream` (NULL = the bank's): translates the batch (as for
+ * sw_score_batch_device: targets at any byte offset, d_lens[k] may be 0, every d_lens[k] <=
+ * max_len) into 6n protein targets, frame-major: translated target f * n + k is frame f of
+ * target k, its codes at d_out + (f * n + k) * out_stride, that offset in
+ * d_out_offsets[f * n + k] and its length in d_out_lens[f * n + k].  Nothing is written past a
+ * translated target's length.  out_stride >= max(max_len / 3, 1), else SW_ERR_ARG.  The reverse
+ * frames read the target from its far end; no reverse complement is made.  Neither penalties
+ * nor a query are needed: a library is translated once and handed to sw_score_batch_device,
+ * sw_estimate_statistics_device and the rest as an ordinary protein batch (whose padding the
+ * caller zeroes, as for any batch).  A multi-device bank runs it on its root.  SW_ERR_ARG: a
+ * NULL bank or buffer, n == 0, 6n >= 2^32.  sw_last_kernel reports "translate n=<n>". */
+sw_status sw_translate_batch_device(sw_bank *bank, const uint8_t *d_residues,
+                                    const uint64_t *d_offsets, const uint32_t *d_lens, size_t n,
+                                    uint32_t max_len, const uint8_t *codon_table, uint8_t *d_out,
+                                    size_t out_stride, uint64_t *d_out_offsets,
+                                    uint32_t *d_out_lens, void *stream);
+
+/* Device buffers, asynchronous on `stream`: scores the six frames of every target against the
+ * loaded query or query set.  With nq = sw_query_count(): d_scores receives the merged nq x n
+ * int32 scores, query-major; d_frames (may be NULL) the nq x n uint8 frames.  The batch runs in
+ * slices of targets whose scratch (six translations at a stride of max_len / 3, their offsets
+ * and lengths, 6 nq scores per target) is bounded by SWBANK_FRAME_MB (MiB, default 256);
+ * slicing cannot change a result.  A slice is translated and its 6 nk translated targets are
+ * scored in ONE sw_score_batch_device_range call over the lengths
+ * [(max(min_len, 2) - 2) / 3, max_len / 3], so the length sort and the balanced ranges see all
+ * frames together; a single query stays on the single-query kernels, multi-device dealing is
+ * that of a forward search; a merge kernel follows.  No best hit is tracked.  A latched hand-off
+ * fault of an earlier device call is returned as by the other device calls; sw_bank_sync waits
+ * for the merge.  SW_ERR_STATE without penalties or a query; SW_ERR_ARG for min_len > max_len, a
+ * NULL buffer (n > 0) or n >= 2^32; n == 0 is SW_OK.  sw_last_kernel reports
+ * "frames nq=<nq> n=<n> slices=<s>"; with sw_bank_set_timing the translation and the merge are
+ * each bracketed as one launch per slice, beside the scoring pass's own. */
+sw_status sw_score_frames_device(sw_bank *bank, const uint8_t *d_residues,
+                                 const uint64_t *d_offsets, const uint32_t *d_lens, size_t n,
+                                 uint32_t min_len, uint32_t max_len, const uint8_t *codon_table,
+                                 int32_t *d_scores, uint8_t *d_frames, void *stream);
+
+/* Host buffers, blocking; the batch as for sw_score_batch (a target outside the residues or a
+ * code of 5 or more is SW_ERR_ARG): uploads it once and calls the device form.  scores_out:
+ * nq x n; frames_out: nq x n, may be NULL. */
+sw_status sw_score_frames(sw_bank *bank, const uint8_t *residues, size_t residues_len,
+                          const uint64_t *offsets, const uint32_t *lens, size_t n,
+                          const uint8_t *codon_table, int32_t *scores_out, uint8_t *frames_out);
+
+/* sw_align_set_hits[_device] on the translation of each hit's frame.  The pair list is that
+ * call's (hit_queries or hits_per_query, hits or h itself, the SW_QUERY_NONE / SW_HIT_NONE
+ * sentinels); frames is the nq x n matrix sw_score_frames writes and is required (NULL:
+ * SW_ERR_ARG).  Hit h (query i, target k) is aligned against frame f = frames[i * n + k] of
+ * target k; only the listed hits are translated.  Every rule of sw_align_set_hits (end, start,
+ * CIGAR preference, empty pair, SW_ALIGN_NO_PATH, the SWBANK_ALIGN_MB budget and its chunks)
+ * holds on the translated target: the record is what that call returns for a batch holding the
+ * translation, except that
+ *   index and id name the DNA target: k, and ids[k] or k;
+ *   flags |= (f % 3) << SW_ALIGN_FRAME_SHIFT, and |= SW_ALIGN_REVERSE for f >= 3 (an empty pair
+ *   too, never a slot that names no pair);
+ *   t_start and t_end are nucleotide positions on the forward target, 0-based, inclusive,
+ *   t_start <= t_end: with the alignment over amino positions a_start..a_end of the frame,
+ *   o = f % 3 and L the target's length,
+ *     forward   t_start = o + 3 a_start,                t_end = o + 3 a_end + 2
+ *     reverse   t_start = L - 1 - (o + 3 a_end + 2),    t_end = L - 1 - (o + 3 a_start)
+ *   (an empty pair keeps 0).
+ * q_*, n_columns, n_identities and the CIGAR stay in amino-acid columns: an identity is a pair
+ * of equal protein codes, a D op consumes one codon.  The device form treats a frame above 5 as
+ * a target without codons (an empty pair, no frame flags); the host form returns SW_ERR_ARG for
+ * a listed pair whose frame is above 5 and for a code of 5 or more in a listed target.
+ * max_len >= every d_lens[k].  sw_last_kernel reports
+ * "align-frame i32 nq=<nq> hits=<n_hits> chunks=<c>". */
+enum { SW_ALIGN_FRAME_SHIFT = 4, SW_ALIGN_FRAME_MASK = 0x30 }; /* flags: f % 3 of the hit's frame */
+
+sw_status sw_align_frame_hits_device(sw_bank *bank, const uint8_t *d_residues,
+                                     const uint64_t *d_offsets, const uint32_t *d_lens,
+                                     const uint64_t *d_ids, size_t n, uint32_t max_len,
+                                     const uint8_t *codon_table, const uint8_t *d_frames,
+                                     const uint32_t *d_hit_queries, size_t hits_per_query,
+                                     const uint64_t *d_hits, size_t n_hits, sw_alignment *d_out,
+                                     uint32_t *d_cigar, uint32_t cigar_stride, void *stream);
+
+sw_status sw_align_frame_hits(sw_bank *bank, const uint8_t *residues, size_t residues_len,
+                              const uint64_t *offsets, const uint32_t *lens, const uint64_t *ids,
+                              size_t n, const uint8_t *codon_table, const uint8_t *frames,
+                              const uint32_t *hit_queries, size_t hits_per_query,
+                              const uint64_t *hits, size_t n_hits, sw_alignment *out,
+                              uint32_t *cigar, size_t cigar_cap, size_t *cigar_used);
 
 /* ---- profiling (≙ the CAPI AFU's cycle counters, capi_sample_aligner/hdl-verliog/afu.v
  *      _DEBUGGING_ "calculation #N completed, runtime: C cycles") ------------------------- */

@@ -25,6 +25,8 @@ struct Pairs {
   // sw_align_strand_hits*: the nq x n strand matrix (NULL: every hit on the forward strand)
   bool strand_call = false;
   const uint8_t* strands = nullptr;
+  // sw_align_frame_hits*: the set call over the translated hits (a protein bank's)
+  bool frame_call = false;
 };
 
 size_t query_count(const sw_bank* b) { return b->qset.size() > 1 ? b->qset.size() : 1; }
@@ -118,8 +120,12 @@ sw_status align_block(sw_bank* b, SwkAlign& p, size_t nh, uint32_t max_len) {
   return SW_OK;
 }
 
-void name_kernel(sw_bank* b, bool set, size_t hits, size_t chunks, bool strand = false) {
-  if (strand)
+void name_kernel(sw_bank* b, bool set, size_t hits, size_t chunks, bool strand = false,
+                 bool frame = false) {
+  if (frame)
+    snprintf(b->last_kernel, sizeof(b->last_kernel), "align-frame i32 nq=%zu hits=%zu chunks=%zu",
+             query_count(b), hits, chunks);
+  else if (strand)
     snprintf(b->last_kernel, sizeof(b->last_kernel), "align-strand i32 nq=%zu hits=%zu chunks=%zu",
              query_count(b), hits, chunks);
   else if (set)
@@ -129,13 +135,18 @@ void name_kernel(sw_bank* b, bool set, size_t hits, size_t chunks, bool strand =
     snprintf(b->last_kernel, sizeof(b->last_kernel), "align i32 hits=%zu chunks=%zu", hits, chunks);
 }
 
-// How every entry opens: a strand call is for DNA banks; a multi-device bank checks the state it
-// holds itself and hands the call to its root (call(root, stream)), where the caller's buffers
-// are.  False on a single bank that may go on; else the call is over and `st` is its status.
+// How every entry opens: a strand call is for DNA banks, a frame call for protein banks; a
+// multi-device bank checks the state it holds itself and hands the call to its root
+// (call(root, stream)), where the caller's buffers are.  False on a single bank that may go on;
+// else the call is over and `st` is its status.
 template <class F>
 bool align_opening(sw_bank* b, const Pairs& pr, void* stream, sw_status& st, F&& call) {
   if (pr.strand_call && b->cfg.alphabet != SW_ALPHABET_DNA) {
     st = fail(b, SW_ERR_UNSUPPORTED, "strand alignments: DNA banks only");
+    return true;
+  }
+  if (pr.frame_call && b->cfg.alphabet != SW_ALPHABET_PROTEIN) {
+    st = fail(b, SW_ERR_UNSUPPORTED, "frame alignments: protein banks only");
     return true;
   }
   if (!b->is_multi()) return false;
@@ -193,7 +204,7 @@ sw_status device_launch(sw_bank* b, const uint8_t* d_res, const uint64_t* d_offs
   if (p.cigar_stride && (st = paths_by_slot(b, p, max_len, hs, chunks)) != SW_OK) return st;
   HIPOK(b, swk_launch_align_flip(&p, hs));  // (a strand call: after the last pass)
   HIPOK(b, hipEventRecord(b->ev_used, hs));
-  name_kernel(b, pr.set, pr.n_hits, chunks, pr.strand_call);
+  name_kernel(b, pr.set, pr.n_hits, chunks, pr.strand_call, pr.frame_call);
   return SW_OK;
 }
 
@@ -466,7 +477,7 @@ sw_status host_call(sw_bank* b, const uint8_t* residues, size_t residues_len,
   }
   HIPOK(b, hipEventRecord(b->ev_used, hs));
   rewrite_records(pr, g, ids, with_cigar, out);
-  name_kernel(b, pr.set, n_hits, chunks, pr.strand_call);
+  name_kernel(b, pr.set, n_hits, chunks, pr.strand_call, pr.frame_call);
   return SW_OK;
 }
 
@@ -539,4 +550,167 @@ extern "C" sw_status sw_align_strand_hits(sw_bank* b, const uint8_t* residues, s
   return host_call(b, residues, residues_len, offsets, lens, ids, n,
                    Pairs{true, hit_queries, hits_per_query, hits, n_hits, true, strands}, out,
                    cigar, cigar_cap, cigar_used);
+}
+
+// ---- the translated search: a hit on its frame ---------------------------------
+// Hit h (query i, target k) is aligned against the translation of frame frames[i * n + k] of its
+// DNA target: the listed hits are translated, one protein target per hit, the set call above
+// aligns query hq[h] against target h of that batch, and the records are rewritten to name the
+// DNA target, its frame and nucleotide coordinates.
+namespace {
+
+Pairs frame_pairs(const uint32_t* hit_queries, size_t hits_per_query, const uint64_t* hits,
+                  size_t n_hits) {
+  Pairs pr{true, hit_queries, hits_per_query, hits, n_hits};
+  pr.frame_call = true;
+  return pr;
+}
+
+// Flags and nucleotide coordinates of a record on frame f of a target of L codes.
+void frame_record(sw_alignment& r, uint32_t f, uint32_t L) {
+  const uint32_t o = f % 3;
+  r.flags |= (o << SW_ALIGN_FRAME_SHIFT) | (f >= 3 ? (uint32_t)SW_ALIGN_REVERSE : 0u);
+  if (r.score <= 0) return;
+  const uint32_t fs = o + 3 * r.t_start, fe = o + 3 * r.t_end + 2;
+  r.t_start = f < 3 ? fs : L - 1 - fe;
+  r.t_end = f < 3 ? fe : L - 1 - fs;
+}
+
+}  // namespace
+
+extern "C" sw_status sw_align_frame_hits_device(sw_bank* b, const uint8_t* d_res,
+                                                const uint64_t* d_offs, const uint32_t* d_lens,
+                                                const uint64_t* d_ids, size_t n, uint32_t max_len,
+                                                const uint8_t* codon_table,
+                                                const uint8_t* d_frames,
+                                                const uint32_t* d_hit_queries,
+                                                size_t hits_per_query, const uint64_t* d_hits,
+                                                size_t n_hits, sw_alignment* d_out,
+                                                uint32_t* d_cigar, uint32_t cigar_stride,
+                                                void* stream) {
+  DevGuard dev_guard(b);  // on the bank's device; the caller's is restored on return (ABI 6)
+  if (!b) return SW_ERR_ARG;
+  const Pairs pr = frame_pairs(d_hit_queries, hits_per_query, d_hits, n_hits);
+  sw_status st;
+  if (align_opening(b, pr, stream, st, [&](sw_bank* r, void* s) {
+        return sw_align_frame_hits_device(r, d_res, d_offs, d_lens, d_ids, n, max_len, codon_table,
+                                          d_frames, d_hit_queries, hits_per_query, d_hits, n_hits,
+                                          d_out, d_cigar, cigar_stride, s);
+      }))
+    return st;
+  uint8_t tab[64];
+  if (!swbank_codon_table(codon_table, tab))
+    return fail(b, SW_ERR_ARG, "a codon table entry is no protein code (>= %d)", SW_PROTEIN_ALPHA);
+  // a hand-off fault latched by an earlier device call is returned before anything runs
+  if (const sw_status fs = take_fault(b, 0); fs != SW_OK) return fs;
+  if ((st = align_ready(b, true)) != SW_OK) return st;
+  if (!d_frames) return fail(b, SW_ERR_ARG, "frame alignments need the frames of the pairs");
+  if (n_hits == 0) return SW_OK;
+  if (!d_res || !d_offs || !d_lens || !d_out || n == 0)
+    return fail(b, SW_ERR_ARG, "null device buffer or an empty batch");
+  if ((st = check_pairs(b, pr, n)) != SW_OK) return st;
+  if (d_cigar && cigar_stride && (uint64_t)n_hits * cigar_stride > 0xFFFFFFFFull)
+    return fail(b, SW_ERR_ARG, "n_hits x cigar_stride must fit 32 bits (cigar_offset)");
+  HIPOK(b, hipSetDevice(b->device));
+  hipStream_t hs = stream_or(b, stream);
+  // one translated hit per slot of the scratch, at the stride of the longest frame
+  const uint32_t cap = max_len / 3;
+  const SlicePlan hp{align16(cap) + 16, n_hits, 1};
+  const size_t nq = query_count(b);
+  // the previous call's use of the scratch, on whichever stream it ran
+  if ((st = scratch_event(b, b->ev_frame, hs)) != SW_OK) return st;
+  if ((st = slice_reserve(b, b->fr_hits, hp, 0, hs)) != SW_OK) return st;
+  HIPOK(b, b->fr_hit_lens.reserve(n_hits));
+  HIPOK(b, b->fr_hit_q.reserve(n_hits));
+  st = timed_on(b, hs, [&] {
+    return swk_translate_hits(d_res, d_offs, d_lens, n, nq, d_frames, d_hit_queries,
+                              hits_per_query, d_hits, n_hits, tab, b->fr_hits.codes.p, hp.stride,
+                              cap, b->fr_hits.offs.p, b->fr_hit_lens.p, b->fr_hit_q.p, hs);
+  });
+  if (st == SW_OK)
+    st = device_call(b, b->fr_hits.codes.p, b->fr_hits.offs.p, b->fr_hit_lens.p, nullptr, n_hits,
+                     cap, frame_pairs(b->fr_hit_q.p, 0, nullptr, n_hits), d_out, d_cigar,
+                     cigar_stride, hs);
+  if (st == SW_OK) {
+    HIPOK(b, hipSetDevice(b->device));
+    st = timed_on(b, hs, [&] {
+      return swk_frame_fixup(d_out, d_lens, d_ids, n, nq, d_frames, d_hit_queries, hits_per_query,
+                             d_hits, n_hits, hs);
+    });
+  }
+  // whatever was launched uses the scratch: the next call is ordered after it in any case
+  const hipError_t er = hipEventRecord(b->ev_frame, hs);
+  if (st != SW_OK) return st;
+  HIPOK(b, er);
+  return SW_OK;
+}
+
+extern "C" sw_status sw_align_frame_hits(sw_bank* b, const uint8_t* residues, size_t residues_len,
+                                         const uint64_t* offsets, const uint32_t* lens,
+                                         const uint64_t* ids, size_t n, const uint8_t* codon_table,
+                                         const uint8_t* frames, const uint32_t* hit_queries,
+                                         size_t hits_per_query, const uint64_t* hits,
+                                         size_t n_hits, sw_alignment* out, uint32_t* cigar,
+                                         size_t cigar_cap, size_t* cigar_used) {
+  DevGuard dev_guard(b);  // on the bank's device; the caller's is restored on return (ABI 6)
+  if (!b) return SW_ERR_ARG;
+  if (cigar_used) *cigar_used = 0;
+  const Pairs pr = frame_pairs(hit_queries, hits_per_query, hits, n_hits);
+  sw_status st;
+  if (align_opening(b, pr, nullptr, st, [&](sw_bank* r, void*) {  // (hit lists are small)
+        return sw_align_frame_hits(r, residues, residues_len, offsets, lens, ids, n, codon_table,
+                                   frames, hit_queries, hits_per_query, hits, n_hits, out, cigar,
+                                   cigar_cap, cigar_used);
+      }))
+    return st;
+  uint8_t tab[64];
+  if (!swbank_codon_table(codon_table, tab))
+    return fail(b, SW_ERR_ARG, "a codon table entry is no protein code (>= %d)", SW_PROTEIN_ALPHA);
+  if ((st = align_ready(b, true)) != SW_OK) return st;
+  if (!frames) return fail(b, SW_ERR_ARG, "frame alignments need the frames of the pairs");
+  if (n_hits == 0) return SW_OK;
+  if (!offsets || !lens || !out) return fail(b, SW_ERR_ARG, "null host buffer");
+  if ((st = check_pairs(b, pr, n)) != SW_OK) return st;
+  // the listed hits, translated: hit h is target h of a protein batch against query hq[h]
+  const size_t nq = query_count(b);
+  std::vector<uint64_t> toffs(n_hits);
+  std::vector<uint32_t> tlens(n_hits, 0), hq(n_hits, SW_QUERY_NONE), hf(n_hits, 0);
+  std::vector<uint8_t> tres;
+  for (size_t h = 0; h < n_hits; ++h) {
+    toffs[h] = tres.size();
+    const uint64_t t = target_of(pr, h);
+    const uint32_t qi = hit_queries ? hit_queries[h] : (uint32_t)(h / hits_per_query);
+    if (qi != SW_QUERY_NONE && qi >= nq)
+      return fail(b, SW_ERR_ARG, "hit %zu: query %u >= nq = %zu", h, qi, nq);
+    if (t == SW_HIT_NONE) continue;
+    if (t >= n)
+      return fail(b, SW_ERR_ARG, "hit %zu: target %llu >= n = %zu", h, (unsigned long long)t, n);
+    if (qi == SW_QUERY_NONE) continue;
+    const uint32_t f = frames[(size_t)qi * n + t];
+    if (f >= SW_FRAME_COUNT) return fail(b, SW_ERR_ARG, "hit %zu: frame %u > 5", h, f);
+    const uint64_t o = offsets[t], l = lens[t];
+    if (l && (!residues || o > residues_len || l > residues_len - o))
+      return fail(b, SW_ERR_ARG, "target %llu outside the residues", (unsigned long long)t);
+    for (uint64_t i = 0; i < l; ++i)
+      if (residues[o + i] >= SW_DNA_ALPHA)
+        return fail(b, SW_ERR_ARG, "target %llu code %u at %llu is no DNA code",
+                    (unsigned long long)t, residues[o + i], (unsigned long long)i);
+    hq[h] = qi;
+    hf[h] = f;
+    tres.resize(tres.size() + l / 3);
+    tlens[h] = l ? (uint32_t)sw_translate_codes(residues + o, l, f, tab, tres.data() + toffs[h]) : 0;
+    tres.resize(toffs[h] + tlens[h]);
+  }
+  if (tres.empty()) tres.push_back(0);
+  st = host_call(b, tres.data(), tres.size(), toffs.data(), tlens.data(), nullptr, n_hits,
+                 frame_pairs(hq.data(), 0, nullptr, n_hits), out, cigar, cigar_cap, cigar_used);
+  if (st != SW_OK) return st;
+  for (size_t h = 0; h < n_hits; ++h) {
+    if (out[h].flags & SW_ALIGN_NO_HIT) continue;  // (index = id = SW_HIT_NONE)
+    const uint64_t t = target_of(pr, h);
+    out[h].index = t;
+    out[h].id = ids ? ids[t] : t;
+    frame_record(out[h], hf[h], lens[t]);
+  }
+  return SW_OK;
 }

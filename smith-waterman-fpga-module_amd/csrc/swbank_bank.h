@@ -7,7 +7,8 @@
 // (alignments of chosen hits, of one query or a query set), swbank_top.hip (the k best hits of
 // every row of a score matrix, the best query of every column), swbank_stat.hip (hit
 // statistics: the seeded shuffle, the score histogram, the estimate, bits and E-values),
-// swbank_strand.hip (both DNA strands: the reverse complement, the strand-merged scores).
+// swbank_strand.hip (both DNA strands: the reverse complement, the strand-merged scores),
+// swbank_frame.hip (the translated search: six-frame translation, frame-merged scores).
 //
 // This header also holds what those units share: the buffer types, which free themselves with
 // the bank (DevBuf, UcBuf, PinBuf), the sliced scratch and the staged host batch (SliceScratch,
@@ -139,6 +140,29 @@ extern "C" hipError_t swk_revcomp_batch(const uint8_t* in, const uint64_t* offs,
                                         uint64_t* out_offs, uint32_t stride, hipStream_t st);
 extern "C" hipError_t swk_strand_merge(int32_t* fwd, const int32_t* rev, uint8_t* strands, size_t n,
                                        size_t k0, size_t nk, size_t nq, hipStream_t st);
+// swbank_kframe.hip: the six-frame translation of a batch (translated target f * n + k at
+// out + (f * n + k) * stride, its offset and length to out_offs / out_lens; cap bounds a
+// translation's length; table: 64 protein codes on the host), the merge of nq rows of 6 * nk slice
+// scores into out[i * n + k0 + k] and frames (optional; a tie is the lowest frame), and for the
+// alignment of chosen hits the translation of each hit's frame (one protein target per hit, its
+// query to out_q, SW_QUERY_NONE for a slot naming no pair) and the records' rewrite
+extern "C" hipError_t swk_translate_batch(const uint8_t* in, const uint64_t* offs,
+                                          const uint32_t* lens, size_t n, const uint8_t* table,
+                                          uint8_t* out, size_t stride, uint32_t cap,
+                                          uint64_t* out_offs, uint32_t* out_lens, hipStream_t st);
+extern "C" hipError_t swk_frame_merge(int32_t* out, const int32_t* slice, uint8_t* frames, size_t n,
+                                      size_t k0, size_t nk, size_t nq, hipStream_t st);
+extern "C" hipError_t swk_translate_hits(const uint8_t* in, const uint64_t* offs,
+                                         const uint32_t* lens, size_t n, size_t nq,
+                                         const uint8_t* frames, const uint32_t* hit_queries,
+                                         size_t hits_per_query, const uint64_t* hits,
+                                         size_t n_hits, const uint8_t* table, uint8_t* out,
+                                         size_t stride, uint32_t cap, uint64_t* out_offs,
+                                         uint32_t* out_lens, uint32_t* out_q, hipStream_t st);
+extern "C" hipError_t swk_frame_fixup(sw_alignment* out, const uint32_t* lens, const uint64_t* ids,
+                                      size_t n, size_t nq, const uint8_t* frames,
+                                      const uint32_t* hit_queries, size_t hits_per_query,
+                                      const uint64_t* hits, size_t n_hits, hipStream_t st);
 extern "C" hipError_t swk_stat_signif(const double* par, const int32_t* hit_scores,
                                       const uint64_t* hits, const uint32_t* lens, size_t k,
                                       size_t nq, double db_size, double* bits, double* evalues,
@@ -528,6 +552,18 @@ struct sw_bank {
   DevBuf<uint8_t> str_hstr;
   DevBuf<int32_t> str_hsc;
   hipEvent_t ev_strand = nullptr;
+  // the translated search (swbank_frame.hip): the six translations of a slice of targets at a
+  // fixed stride, their offsets and the slice's 6 nq rows of scores (fr_slice), their lengths
+  // (fr_lens); the translated hits of an alignment call with their offsets (fr_hits), lengths and
+  // queries; the host forms' batch (fr_host), merged scores, frames and records' inputs on the
+  // device; ev_frame follows the last call's use of them, on whichever stream it ran, and the next
+  // call's stream waits for it
+  SliceScratch fr_slice, fr_hits;
+  StagedBatch fr_host;
+  DevBuf<uint32_t> fr_lens, fr_hit_lens, fr_hit_q;
+  DevBuf<uint8_t> fr_hfr;
+  DevBuf<int32_t> fr_hsc;
+  hipEvent_t ev_frame = nullptr;
   struct Seg { int W; size_t off, off16; };  // rows = W*R (last may be shorter); word offsets
                                               // in qtab and qtab16
   std::vector<Seg> segs;

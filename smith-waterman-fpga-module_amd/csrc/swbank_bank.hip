@@ -174,6 +174,7 @@ extern "C" void sw_bank_destroy(sw_bank* b) {
   if (b->ev_top) (void)hipEventSynchronize(b->ev_top);  // the last top-hits call, on any stream
   if (b->ev_stat) (void)hipEventSynchronize(b->ev_stat);  // ... significance call
   if (b->ev_strand) (void)hipEventSynchronize(b->ev_strand);  // ... strand call
+  if (b->ev_frame) (void)hipEventSynchronize(b->ev_frame);  // ... translated-search call
   uint64_t nl;
   double pm, sm;
   (void)sw_bank_timing(b, &nl, &pm, &sm);
@@ -183,6 +184,7 @@ extern "C" void sw_bank_destroy(sw_bank* b) {
   if (b->ev_top) (void)hipEventDestroy(b->ev_top);
   if (b->ev_stat) (void)hipEventDestroy(b->ev_stat);
   if (b->ev_strand) (void)hipEventDestroy(b->ev_strand);
+  if (b->ev_frame) (void)hipEventDestroy(b->ev_frame);
   if (b->ev_join) (void)hipEventDestroy(b->ev_join);
   for (hipEvent_t e : b->deal_ev) (void)hipEventDestroy(e);
   if (b->copy_stream) (void)hipStreamSynchronize(b->copy_stream);
@@ -352,6 +354,7 @@ extern "C" sw_status sw_bank_sync(sw_bank* b) {
   if (e == hipSuccess && b->ev_top) e = hipEventSynchronize(b->ev_top);  // ... of a top-hits call
   if (e == hipSuccess && b->ev_stat) e = hipEventSynchronize(b->ev_stat);  // ... significance
   if (e == hipSuccess && b->ev_strand) e = hipEventSynchronize(b->ev_strand);  // ... strands
+  if (e == hipSuccess && b->ev_frame) e = hipEventSynchronize(b->ev_frame);  // ... frames
   if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
   (void)hipSetDevice(cur);
   HIPOK(b, e);

@@ -9,7 +9,7 @@
  *
  * Usage: swbank -q query.fa -l library.fa [-p match,mismatch,open,extend] [-P] [-g]
  *               [-d device[,device...]] [-o out.txt] [-T] [-R scores.txt] [-b] [-A k]
- *               [-E rounds[,seed]] [-S lambda,K] [-B]
+ *               [-E rounds[,seed]] [-S lambda,K] [-B] [-X]
  *   -p  penalties (default 5,-4,-12,-4: ScoreBank_v1_tb.sv:16-19, data/smith-waterman.py:6-10)
  *   -P  protein mode (BLOSUM62; -p gives only open,extend)      -g  Gotoh gap model
  *   -T  testbench transcript format "@     0ns: %10s score: \t%d"
@@ -40,6 +40,18 @@
  *       (two strands are a library twice the size; the reference, run with -3, pins no such
  *       convention), printed as E(2n); -E still fits lambda and K on forward shuffles.  The -R
  *       file keeps its layout (scores only).  Not with -P.
+ *   -X  translated search (sw_score_frames; the FASTA suite's tfastx without frameshifts): -q is
+ *       a protein, -l a DNA library; every record is translated in its three forward and three
+ *       reverse reading frames, each frame is scored with BLOSUM62 (-X implies -P's matrix and
+ *       its -11,-1 default; -p gives open,extend), and the best frame's score is printed with
+ *       " [+1]", " [+2]", " [+3]", " [-1]", " [-2]" or " [-3]" after it (a tie: the first of
+ *       these).  -A aligns each hit on its frame (sw_align_frame_hits), prints the frame after
+ *       ">>name (len nt)" and the overlap in aa columns with the record's 1-based nucleotide
+ *       range, high to low for a reverse frame.  With -E / -S the E-values take db_size = 6 x
+ *       the record count and the frame's length in codons, printed as E(6n); -E fits lambda and K
+ *       on shuffles of the library's six translations (made here with sw_translate_codes and
+ *       handed to sw_estimate_statistics as the protein batch they are).  Not with -B (the
+ *       reverse frames are already searched).
  *   -b  also print the bank's best hit ("best: >name score: S", ≙ max / vld_max) to stderr
  * FASTA: '>' starts a record (name = first token); sequence lines are concatenated; CR/LF,
  * blank lines and lower case are accepted; bytes outside the alphabet encode to N (DNA) or X
@@ -128,7 +140,8 @@ static void usage(const char *argv0) {
   fprintf(stderr,
           "usage: %s -q query.fa -l library.fa [-p match,mismatch,open,extend] [-P] [-g]\n"
           "          [-d device[,device...]] [-o out.txt] [-T] [-R scores.txt] [-b] [-A k]\n"
-          "          [-E rounds[,seed]] [-S lambda,K] [-B]\n",
+          "          [-E rounds[,seed]] [-S lambda,K] [-B] [-X]\n"
+          "  -X: protein query against a DNA library in six reading frames; not with -B\n",
           argv0);
 }
 
@@ -141,10 +154,14 @@ static int by_score(const void *a, const void *b) {
   return x < y ? -1 : x > y;
 }
 
+static const char *const kFrameTag[SW_FRAME_COUNT] = {" [+1]", " [+2]", " [+3]",
+                                                      " [-1]", " [-2]", " [-3]"};
+
 static int print_alignments(FILE *out, sw_bank *bank, const uint8_t *res, size_t total,
                             const uint64_t *offs, const uint32_t *lens, const int32_t *scores,
                             const fasta_t *lib, size_t asked, const char *unit,
-                            const sw_statistics *stats, const uint8_t *strands) {
+                            const sw_statistics *stats, const uint8_t *strands,
+                            const uint8_t *frames) {
   const size_t k = asked < lib->n ? asked : lib->n;
   const int on_device = asked <= SW_TOP_MAX_K; /* (what -A asked for picks the path) */
   uint64_t *order = malloc((on_device ? k : lib->n) * sizeof(uint64_t));
@@ -169,6 +186,9 @@ static int print_alignments(FILE *out, sw_bank *bank, const uint8_t *res, size_t
     cig = malloc(cap * sizeof(uint32_t));
     if (!cig)
       st = SW_ERR_NOMEM;
+    else if (frames) /* -X: one query, the [1, k] layout */
+      st = sw_align_frame_hits(bank, res, total, offs, lens, NULL, lib->n, NULL, frames, NULL, k,
+                               order, k, al, cig, cap, &used);
     else if (strands) /* -B: one query, the [1, k] layout */
       st = sw_align_strand_hits(bank, res, total, offs, lens, NULL, lib->n, strands, NULL, k, order,
                                 k, al, cig, cap, &used);
@@ -181,19 +201,24 @@ static int print_alignments(FILE *out, sw_bank *bank, const uint8_t *res, size_t
     for (size_t i = 0; i < k; ++i) {
       const sw_alignment *a = &al[i];
       const int rev = (a->flags & SW_ALIGN_REVERSE) != 0;
-      const size_t db = strands ? 2 * lib->n : lib->n; /* two strands: twice the library */
-      fprintf(out, ">>%s (%u %s)%s\n s-w opt: %d", lib->names[a->index], lens[a->index], unit,
-              strands ? (rev ? " [r]" : " [f]") : "", a->score);
+      /* two strands: twice the library; six frames: six times */
+      const size_t db = frames ? SW_FRAME_COUNT * lib->n : strands ? 2 * lib->n : lib->n;
+      const uint32_t fo = (a->flags & SW_ALIGN_FRAME_MASK) >> SW_ALIGN_FRAME_SHIFT;
+      /* the length the statistics see: the record's, or (-X) its frame's in codons */
+      const uint32_t slen = frames ? (lens[a->index] - fo) / 3 : lens[a->index];
+      fprintf(out, ">>%s (%u %s)%s\n s-w opt: %d", lib->names[a->index], lens[a->index],
+              frames ? "nt" : unit,
+              frames ? kFrameTag[fo + (rev ? 3 : 0)] : strands ? (rev ? " [r]" : " [f]") : "",
+              a->score);
       double bits, ev;
-      if (stats && sw_hit_significance(stats, &a->score, &lens[a->index], 1, db, &bits, &ev) ==
-                       SW_OK)
+      if (stats && sw_hit_significance(stats, &a->score, &slen, 1, db, &bits, &ev) == SW_OK)
         fprintf(out, "  bits: %.1f E(%zu): %.2g", bits, db, ev);
       fputc('\n', out);
       if (a->flags & SW_ALIGN_EMPTY) continue;
       /* the target range of a reverse hit runs high to low on the forward record */
       const uint32_t t_from = rev ? a->t_end + 1 : a->t_start + 1;
       const uint32_t t_to = rev ? a->t_start + 1 : a->t_end + 1;
-      if ((a->flags & ~(uint32_t)SW_ALIGN_REVERSE) == 0) {
+      if ((a->flags & ~(uint32_t)(SW_ALIGN_REVERSE | SW_ALIGN_FRAME_MASK)) == 0) {
         const double pct = 100.0 * a->n_identities / a->n_columns;
         fprintf(out,
                 "Smith-Waterman score: %d; %.1f%% identity (%.1f%% similar) in %u %s overlap "
@@ -221,7 +246,7 @@ static int print_alignments(FILE *out, sw_bank *bank, const uint8_t *res, size_t
 
 int main(int argc, char **argv) {
   const char *qpath = NULL, *lpath = NULL, *opath = NULL, *pen = NULL, *rpath = NULL;
-  int protein = 0, gotoh = 0, device = -1, transcript = 0, best = 0, both = 0, opt;
+  int protein = 0, gotoh = 0, device = -1, transcript = 0, best = 0, both = 0, xlate = 0, opt;
   int ndev = 0, devs[SW_MAX_DEVICES];
   long nalign = 0;
   int have_stats = 0; /* 1: -S (given), 2: -E (estimated) */
@@ -229,7 +254,7 @@ int main(int argc, char **argv) {
   unsigned long long stat_seed = 0;
   sw_statistics stats;
   memset(&stats, 0, sizeof(stats));
-  while ((opt = getopt(argc, argv, "q:l:p:Pgd:o:TR:bA:E:S:Bh")) != -1) {
+  while ((opt = getopt(argc, argv, "q:l:p:Pgd:o:TR:bA:E:S:BXh")) != -1) {
     switch (opt) {
       case 'q': qpath = optarg; break;
       case 'l': lpath = optarg; break;
@@ -251,6 +276,7 @@ int main(int argc, char **argv) {
       }
       case 'b': best = 1; break;
       case 'B': both = 1; break;
+      case 'X': xlate = protein = 1; break;
       case 'A': {
         char *end;
         nalign = strtol(optarg, &end, 10);
@@ -284,6 +310,11 @@ int main(int argc, char **argv) {
   }
   if (!qpath || !lpath) {
     fprintf(stderr, "Input files missing\n");
+    usage(argv[0]);
+    return 1;
+  }
+  if (xlate && both) {
+    fprintf(stderr, "-X searches the reverse frames already: not with -B\n");
     usage(argv[0]);
     return 1;
   }
@@ -347,21 +378,46 @@ int main(int argc, char **argv) {
   uint32_t *lens = malloc((lib.n + 1) * sizeof(uint32_t));
   int32_t *scores = malloc((lib.n + 1) * sizeof(int32_t));
   uint8_t *strands = both ? calloc(lib.n + 1, 1) : NULL;
-  if (!res || !offs || !lens || !scores || (both && !strands)) st = SW_ERR_NOMEM;
+  uint8_t *frames = xlate ? calloc(lib.n + 1, 1) : NULL;
+  if (!res || !offs || !lens || !scores || (both && !strands) || (xlate && !frames))
+    st = SW_ERR_NOMEM;
   size_t pos = 0;
   for (size_t k = 0; st == SW_OK && k < lib.n; ++k) {
     size_t l = strlen(lib.seqs[k]);
-    sw_encode_ascii(alphabet, lib.seqs[k], l, res + pos);
+    sw_encode_ascii(xlate ? SW_ALPHABET_DNA : alphabet, lib.seqs[k], l, res + pos);
     offs[k] = pos;
     lens[k] = (uint32_t)l;
     pos += l;
   }
   if (st == SW_OK)
-    st = both ? sw_score_strands(bank, res, total, offs, lens, lib.n, scores, strands)
-              : sw_score_batch(bank, res, total, offs, lens, NULL, lib.n, scores);
-  if (st == SW_OK && have_stats == 2 && lib.n)
+    st = xlate  ? sw_score_frames(bank, res, total, offs, lens, lib.n, NULL, scores, frames)
+         : both ? sw_score_strands(bank, res, total, offs, lens, lib.n, scores, strands)
+                : sw_score_batch(bank, res, total, offs, lens, NULL, lib.n, scores);
+  if (st == SW_OK && have_stats == 2 && lib.n && xlate) {
+    /* the estimate shuffles the batch it is given: give it the six translations, frame-major */
+    const size_t tn = SW_FRAME_COUNT * lib.n;
+    uint8_t *tres = malloc(2 * total + 1);
+    uint64_t *toffs = malloc(tn * sizeof(uint64_t));
+    uint32_t *tlens = malloc(tn * sizeof(uint32_t));
+    size_t tpos = 0;
+    if (!tres || !toffs || !tlens) st = SW_ERR_NOMEM;
+    for (size_t s = 0; st == SW_OK && s < tn; ++s) {
+      const size_t k = s % lib.n;
+      toffs[s] = tpos;
+      tlens[s] = (uint32_t)sw_translate_codes(res + offs[k], lens[k], (uint32_t)(s / lib.n), NULL,
+                                              tres + tpos);
+      tpos += tlens[s];
+    }
+    if (st == SW_OK)
+      st = sw_estimate_statistics(bank, tres, tpos, toffs, tlens, tn, stat_seed,
+                                  (uint32_t)stat_rounds, &stats);
+    free(tres);
+    free(toffs);
+    free(tlens);
+  } else if (st == SW_OK && have_stats == 2 && lib.n) {
     st = sw_estimate_statistics(bank, res, total, offs, lens, lib.n, stat_seed,
                                 (uint32_t)stat_rounds, &stats);
+  }
   if (have_stats == 1) stats.query_len = (uint32_t)qlen;
   if (st != SW_OK) {
     fprintf(stderr, "swbank: %s: %s\n", sw_status_string(st), sw_last_error(bank));
@@ -376,7 +432,9 @@ int main(int argc, char **argv) {
   for (size_t k = 0; k < lib.n; ++k) {
     char nm[256];
     snprintf(nm, sizeof(nm), ">%s", lib.names[k]);
-    const char *sd = both ? (strands[k] ? " [r]" : " [f]") : "";
+    const char *sd = xlate  ? kFrameTag[frames[k] < SW_FRAME_COUNT ? frames[k] : 0]
+                     : both ? (strands[k] ? " [r]" : " [f]")
+                            : "";
     if (transcript)
       fprintf(out, "@%6dns: %10s score: \t%10d%s\n", 0, nm, scores[k], sd);
     else
@@ -387,7 +445,7 @@ int main(int argc, char **argv) {
             (unsigned long long)stats.n_samples);
   if (nalign > 0 && lib.n) {
     int rc = print_alignments(out, bank, res, total, offs, lens, scores, &lib, (size_t)nalign,
-                              protein ? "aa" : "nt", have_stats ? &stats : NULL, strands);
+                              protein ? "aa" : "nt", have_stats ? &stats : NULL, strands, frames);
     if (rc) {
       if (opath) fclose(out);
       sw_bank_destroy(bank);
@@ -397,12 +455,14 @@ int main(int argc, char **argv) {
   if (opath) fclose(out);
   uint64_t bid = 0;
   int32_t bsc = 0;
-  /* (-B tracks no best hit on the device: the lowest index with the best merged score) */
+  /* (-B and -X track no best hit on the device: the lowest index with the best merged score) */
   if (best && lib.n &&
-      (both ? sw_best_hit(bank, scores, NULL, lib.n, &bid, &bsc)
-            : sw_batch_best(bank, &bid, &bsc, NULL)) == SW_OK)
+      (both || xlate ? sw_best_hit(bank, scores, NULL, lib.n, &bid, &bsc)
+                     : sw_batch_best(bank, &bid, &bsc, NULL)) == SW_OK)
     fprintf(stderr, "best: >%s score: %d%s\n", lib.names[bid], bsc,
-            both ? (strands[bid] ? " [r]" : " [f]") : "");
+            xlate  ? kFrameTag[frames[bid] < SW_FRAME_COUNT ? frames[bid] : 0]
+            : both ? (strands[bid] ? " [r]" : " [f]")
+                   : "");
   if (rpath) { /* ssearch36 -R layout (data/score500.txt:1-3,502-503) */
     FILE *rf = fopen(rpath, "w");
     if (!rf) {
@@ -432,5 +492,6 @@ int main(int argc, char **argv) {
   free(lens);
   free(scores);
   free(strands);
+  free(frames);
   return 0;
 }

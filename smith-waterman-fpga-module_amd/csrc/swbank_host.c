@@ -100,6 +100,41 @@ size_t sw_revcomp_codes(const uint8_t *codes, size_t n, uint8_t *out) {
   return n;
 }
 
+/* The genetic code a call uses, as 64 protein codes indexed c0 * 16 + c1 * 4 + c2 over the DNA
+ * codes T, C, A, G: the caller's table, or for NULL the standard code.  0 (nothing usable) when
+ * an entry is no protein code.  Shared with swbank_frame.hip and swbank_align.hip. */
+int swbank_codon_table(const uint8_t *user, uint8_t out[64]) {
+  static const char kStandard[] =
+      "FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG";
+  static const char kLetters[] = "ARNDCQEGHILKMFPSTWYVBZX*";
+  for (int i = 0; i < 64; ++i) {
+    if (user) {
+      if (user[i] >= SW_PROTEIN_ALPHA) return 0;
+      out[i] = user[i];
+    } else {
+      out[i] = (uint8_t)(strchr(kLetters, kStandard[i]) - kLetters);
+    }
+  }
+  return 1;
+}
+
+size_t sw_translate_codes(const uint8_t *codes, size_t n, uint32_t frame,
+                          const uint8_t *codon_table, uint8_t *out) {
+  uint8_t tab[64];
+  if (!codes || !out || frame >= SW_FRAME_COUNT || !swbank_codon_table(codon_table, tab)) return 0;
+  const size_t o = frame % 3, nc = n >= o + 3 ? (n - o) / 3 : 0;
+  for (size_t j = 0; j < nc; ++j) {
+    uint8_t c[3];
+    for (size_t i = 0; i < 3; ++i) {
+      const size_t s = o + 3 * j + i;
+      const uint8_t x = frame < 3 ? codes[s] : codes[n - 1 - s];
+      c[i] = (uint8_t)(frame >= 3 && x < 4 ? x ^ 2 : x); /* the reverse frames: rc, read in place */
+    }
+    out[j] = (c[0] | c[1] | c[2]) < 4 ? tab[c[0] * 16 + c[1] * 4 + c[2]] : 22; /* X */
+  }
+  return nc;
+}
+
 /* BLOSUM62 in NCBI order ARNDCQEGHILKMFPSTWYVBZX*. */
 static const int8_t kBlosum62[SW_PROTEIN_ALPHA][SW_PROTEIN_ALPHA] = {
     {4, -1, -2, -2, 0, -1, -1, 0, -2, -1, -1, -1, -1, -2, -1, 1, 0, -3, -2, 0, -2, -1, 0, -4},

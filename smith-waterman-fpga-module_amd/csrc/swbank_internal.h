@@ -113,6 +113,13 @@ typedef struct SwkDeal {
   unsigned nib; /* codes written 4-bit (SWK_PACK_NIBBLE: low nibble first), stride in bytes */
 } SwkDeal;
 
+/* swbank_host.c: the genetic code of a translated-search call as 64 protein codes -- the
+ * caller's table, or the standard code for NULL; 0 when an entry is no protein code. */
+#ifdef __cplusplus
+extern "C"
+#endif
+int swbank_codon_table(const unsigned char* user, unsigned char out[64]);
+
 #ifdef __cplusplus
 /* (declared here so the definition in swbank_ktile.hip and the call in swbank_stream.hip are
  * checked against one signature) */

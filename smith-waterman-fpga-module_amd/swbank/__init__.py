@@ -54,6 +54,8 @@ EXPORTS = (
     "sw_hit_significance", "sw_hit_significance_device",
     "sw_revcomp_codes", "sw_revcomp_batch_device", "sw_score_strands",
     "sw_score_strands_device", "sw_align_strand_hits", "sw_align_strand_hits_device",
+    "sw_translate_codes", "sw_translate_batch_device", "sw_score_frames",
+    "sw_score_frames_device", "sw_align_frame_hits", "sw_align_frame_hits_device",
 )
 ABI_VERSION = 6
 COUNTERS = ("stream_calls", "stream_reruns", "stream_declined", "chunked_calls", "device_sorts",
@@ -65,6 +67,11 @@ CIGAR_M, CIGAR_I, CIGAR_D = 0, 1, 2          # BAM codes: I consumes query only,
 ALIGN_EMPTY, ALIGN_NO_PATH = 1, 2            # sw_alignment.flags
 ALIGN_NO_HIT = 4                             # ... the slot named no pair (with ALIGN_EMPTY)
 ALIGN_REVERSE = 8                            # ... aligned against the target's reverse complement
+ALIGN_FRAME_SHIFT, ALIGN_FRAME_MASK = 4, 0x30  # ... f % 3 of a translated hit's reading frame
+_ALIGN_WHERE = ALIGN_REVERSE | ALIGN_FRAME_MASK  # (flags that say where a hit lies, not how)
+FRAME_COUNT = 6                              # SW_FRAME_COUNT: reading frames of a DNA target
+FRAME_TAGS = ("+1", "+2", "+3", "-1", "-2", "-3")
+STANDARD_CODE = "FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG"
 RECORD_BYTES, RECORD_MAX_BASES = 64, 232
 TOP_MAX_K = 4096                             # SW_TOP_MAX_K: the largest k of the top-hits calls
 HIT_NONE = 0xFFFFFFFFFFFFFFFF                # SW_HIT_NONE: a hit slot past the row's count
@@ -145,13 +152,19 @@ class Alignment:
 
     @property
     def has_path(self) -> bool:
-        return self.flags & ~ALIGN_REVERSE == 0
+        return self.flags & ~_ALIGN_WHERE == 0
 
     @property
     def reverse(self) -> bool:
         """The hit lies on the reverse strand (ALIGN_REVERSE): aligned against the reverse
         complement of its target, t_start / t_end given on the forward target."""
         return bool(self.flags & ALIGN_REVERSE)
+
+    @property
+    def frame(self) -> int:
+        """The reading frame 0..5 of a translated hit (align_frame_hits): frames 0..2 forward,
+        3..5 those of the reverse complement; t_start / t_end are nucleotide positions."""
+        return ((self.flags & ALIGN_FRAME_MASK) >> ALIGN_FRAME_SHIFT) + (3 if self.reverse else 0)
 
 
 def cigar_string(ops) -> str:
@@ -168,7 +181,7 @@ def alignments_from(records: np.ndarray, cigar: np.ndarray) -> list:
     out = []
     for r in records:
         ops = ()
-        if int(r["flags"]) & ~ALIGN_REVERSE == 0:
+        if int(r["flags"]) & ~_ALIGN_WHERE == 0:
             ops = tuple(int(x) for x in cigar[int(r["cigar_offset"]):
                                               int(r["cigar_offset"]) + int(r["cigar_len"])])
         out.append(Alignment(int(r["index"]), int(r["id"]), int(r["score"]), int(r["flags"]),
@@ -267,6 +280,13 @@ def lib() -> ctypes.CDLL:
         "sw_align_strand_hits": (i32, [P, P, sz, P, P, P, sz, P, P, sz, P, sz, P, P, sz, P]),
         "sw_align_strand_hits_device": (i32, [P, P, P, P, P, sz, u32, P, P, sz, P, sz, P, P, u32,
                                               P]),
+        "sw_translate_codes": (sz, [P, sz, u32, P, P]),
+        "sw_translate_batch_device": (i32, [P, P, P, P, sz, u32, P, P, sz, P, P, P]),
+        "sw_score_frames": (i32, [P, P, sz, P, P, sz, P, P, P]),
+        "sw_score_frames_device": (i32, [P, P, P, P, sz, u32, u32, P, P, P, P]),
+        "sw_align_frame_hits": (i32, [P, P, sz, P, P, P, sz, P, P, P, sz, P, sz, P, P, sz, P]),
+        "sw_align_frame_hits_device": (i32, [P, P, P, P, P, sz, u32, P, P, P, sz, P, sz, P, P, u32,
+                                             P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -348,6 +368,31 @@ def revcomp(codes) -> np.ndarray:
     if a.size:
         lib().sw_revcomp_codes(_p(a), a.size, _p(out))
     return out
+
+
+def _codon_table(table) -> Optional[np.ndarray]:
+    """A caller's genetic code as the 64 protein codes the C ABI takes (None: the standard
+    code): 64 letters of ARNDCQEGHILKMFPSTWYVBZX*, or 64 codes."""
+    if table is None:
+        return None
+    t = encode(table, ALPHABET_PROTEIN) if isinstance(table, (str, bytes)) else \
+        np.ascontiguousarray(table, dtype=np.uint8).reshape(-1)
+    if t.size != 64:
+        raise ValueError("a codon table has 64 entries")
+    return t
+
+
+def translate_codes(codes, frame: int, codon_table=None) -> np.ndarray:
+    """sw_translate_codes: the protein codes of reading frame `frame` (0..2 forward, 3..5 those
+    of the reverse complement) of DNA codes; a codon holding N is X, a stop is *."""
+    a = np.ascontiguousarray(codes, dtype=np.uint8).reshape(-1)
+    tab = _codon_table(codon_table)
+    if not 0 <= frame < FRAME_COUNT or (tab is not None and tab.max() >= PROTEIN_ALPHA):
+        raise ValueError("frame 0..5 and a table of protein codes")
+    out = np.empty(max(a.size // 3, 1), dtype=np.uint8)
+    n = lib().sw_translate_codes(_p(a), a.size, frame, _p(tab) if tab is not None else None,
+                                 _p(out)) if a.size else 0
+    return out[:n]
 
 
 def fill_matrix(alphabet: int, match: int = 5, mismatch: int = -4) -> np.ndarray:
@@ -870,6 +915,99 @@ class ScoreBank:
             self._h, d_res or None, d_offs or None, d_lens or None, d_ids or None, n, max_len,
             d_strands or None, d_hit_queries or None, hits_per_query, d_hits or None, n_hits,
             d_out or None, d_cigar or None, cigar_stride, stream or None))
+
+    # the translated search: a protein query against DNA in six reading frames
+    def translate_batch_device(self, d_res: int, d_offs: int, d_lens: int, n: int, max_len: int,
+                               d_out: int, out_stride: int, d_out_offs: int, d_out_lens: int,
+                               codon_table=None, stream: int = 0):
+        """sw_translate_batch_device: device pointers (ints); the 6 n translations of the DNA
+        batch, frame-major (f * n + k), at d_out + (f * n + k) * out_stride, with their offsets
+        and lengths in d_out_offs / d_out_lens.  Async on `stream` (0: the bank's own stream;
+        sync() before reading)."""
+        tab = _codon_table(codon_table)
+        self._check(lib().sw_translate_batch_device(
+            self._h, d_res or None, d_offs or None, d_lens or None, n, max_len,
+            _p(tab) if tab is not None else None, d_out or None, out_stride, d_out_offs or None,
+            d_out_lens or None, stream or None))
+
+    def score_frames_device(self, d_res: int, d_offs: int, d_lens: int, n: int, max_len: int,
+                            d_scores: int, d_frames: int = 0, min_len: int = 0,
+                            codon_table=None, stream: int = 0):
+        """sw_score_frames_device: device pointers (ints); d_scores receives the nq x n int32
+        best-frame scores of the DNA batch against the protein queries, d_frames (optional) the
+        nq x n uint8 frames (the lowest frame that reaches the score).  Async on `stream`."""
+        tab = _codon_table(codon_table)
+        self._check(lib().sw_score_frames_device(
+            self._h, d_res or None, d_offs or None, d_lens or None, n, min_len, max_len,
+            _p(tab) if tab is not None else None, d_scores or None, d_frames or None,
+            stream or None))
+
+    def score_frames(self, residues: np.ndarray, offsets: np.ndarray, lens: np.ndarray,
+                     codon_table=None):
+        """sw_score_frames: (scores int32, frames uint8) of the host DNA batch over its six
+        reading frames, [n] for one loaded query, [nq, n] for a query set."""
+        res, offs, ln, _ = validate_batch(residues, offsets, lens)
+        tab = _codon_table(codon_table)
+        nq, n = max(self.query_count(), 1), len(ln)
+        sc = np.zeros(nq * max(n, 1), np.int32)
+        fr = np.zeros(nq * max(n, 1), np.uint8)
+        self._check(lib().sw_score_frames(self._h, _p(res), res.size, _p(offs), _p(ln), n,
+                                          _p(tab) if tab is not None else None, _p(sc), _p(fr)))
+        scores = sc[:nq * n].reshape(nq, n)
+        frames = fr[:nq * n].reshape(nq, n)
+        return (scores[0], frames[0]) if nq == 1 else (scores, frames)
+
+    def align_frame_hits(self, residues: np.ndarray, offsets: np.ndarray, lens: np.ndarray,
+                         frames, hits=None, hit_queries=None, hits_per_query: int = 0,
+                         ids: Optional[np.ndarray] = None, cigar_cap: Optional[int] = None,
+                         n_hits: Optional[int] = None, codon_table=None) -> list:
+        """sw_align_frame_hits: align_set_hits on the translation of each hit's frame, `frames`
+        the [nq, n] matrix of score_frames.  Alignment.frame is the hit's frame, t_start / t_end
+        are nucleotide positions on the forward target; the query coordinates, the counts and the
+        CIGAR stay in amino-acid columns."""
+        res, offs, ln, idv = validate_batch(residues, offsets, lens, ids)
+        tab = _codon_table(codon_table)
+        fv = None
+        if frames is not None:
+            fv = np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1)
+            if fv.size != max(self.query_count(), 1) * len(ln):
+                raise ValueError("frames: nq x n entries")
+        hv = None if hits is None else np.ascontiguousarray(hits, dtype=np.uint64).reshape(-1)
+        hq = None if hit_queries is None else \
+            np.ascontiguousarray(hit_queries, dtype=np.uint32).reshape(-1)
+        if n_hits is None:
+            n_hits = len(hv) if hv is not None else len(hq) if hq is not None else len(ln)
+        if (hv is not None and len(hv) < n_hits) or (hq is not None and len(hq) < n_hits):
+            raise ValueError("hits / hit_queries shorter than n_hits")
+        out = np.zeros(max(n_hits, 1), dtype=ALIGNMENT_DTYPE)
+        if cigar_cap is None:  # runs alternate with M runs: at most 2 x columns + 1 ops a path
+            tv = hv[:n_hits] if hv is not None else np.arange(min(n_hits, len(ln)), dtype=np.uint64)
+            sel = tv[tv < len(ln)].astype(np.int64)
+            cigar_cap = 2 * int((ln[sel].astype(np.int64) // 3).sum()) + n_hits
+        cig = np.zeros(max(cigar_cap, 1), dtype=np.uint32)
+        used = ctypes.c_size_t()
+        self._check(lib().sw_align_frame_hits(
+            self._h, _p(res), res.size, _p(offs), _p(ln), _p(idv) if idv is not None else None,
+            len(ln), _p(tab) if tab is not None else None, _p(fv) if fv is not None else None,
+            _p(hq) if hq is not None else None, hits_per_query,
+            _p(hv) if hv is not None else None, n_hits, _p(out),
+            _p(cig) if cigar_cap else None, cigar_cap, ctypes.byref(used)))
+        return alignments_from(out[:n_hits], cig)
+
+    def align_frame_hits_device(self, d_res: int, d_offs: int, d_lens: int, n: int, max_len: int,
+                                n_hits: int, d_out: int, d_frames: int, d_hits: int = 0,
+                                d_hit_queries: int = 0, hits_per_query: int = 0,
+                                d_cigar: int = 0, cigar_stride: int = 0, stream: int = 0,
+                                d_ids: int = 0, codon_table=None):
+        """sw_align_frame_hits_device: align_set_hits_device on the translation of each hit's
+        frame, d_frames the nq x n uint8 frame matrix score_frames_device writes.  Async on
+        `stream` (0: the bank's own stream; sync() before reading)."""
+        tab = _codon_table(codon_table)
+        self._check(lib().sw_align_frame_hits_device(
+            self._h, d_res or None, d_offs or None, d_lens or None, d_ids or None, n, max_len,
+            _p(tab) if tab is not None else None, d_frames or None, d_hit_queries or None,
+            hits_per_query, d_hits or None, n_hits, d_out or None, d_cigar or None, cigar_stride,
+            stream or None))
 
     def counters(self) -> dict:
         """sw_bank_counters: feeder / fallback counts since the bank was created."""
