@@ -4,7 +4,8 @@ The GPU tests compare the alignment kernels' CIGARs with align_cases.ref_path on
 by tests/align_cases.py.  That proves something only if (1) the reference is right where the
 answer is known, and (2) the inputs put a live gap, a tie or a window edge where they claim to.
 Building a family checks (2) (it raises otherwise); this module builds every one and checks its
-shape, and checks (1) on the ssearch36 fixture, the corner-turning pair and random pairs."""
+shape, and checks (1) on the ssearch36 fixture, the corner-turning pair and random pairs.  The
+matrix family of tests/matrix_cases.py (asymmetric matrices) is live by matrix mutants: section 3."""
 import collections
 import os
 
@@ -15,6 +16,7 @@ from oracle import oracle as O
 
 import align_cases as C
 import align_check as AC
+import matrix_cases as MC
 
 ABC = [(tag, model) for tag in C.DNA_SETS for model in C.MODELS]
 
@@ -185,3 +187,66 @@ def test_reuse_case(model):
     assert all(a > 600 or a <= 40 for a in lens)
     assert 0 in lens and sorted(order2[1:-1]) == sorted(g.hits) and order2[1:-1] != g.hits
     assert len(set(g.hits)) < len(g.hits)
+
+
+# ---- 3. asymmetric matrices ----------------------------------------------------------------------
+def check_mutant(g, P, name, sub2):
+    """A matrix mutant changes the score of >= 80 % of the group's positive hits, and the
+    coordinates or the ops of at least one record.  Prints the figures (pytest -s)."""
+    share, moved = MC.mutant_share(g, P, sub2), MC.mutant_moved(g, P, sub2)
+    print(f"\n    {g.name} {name}: {100 * share:.0f} % ({moved})", end="")
+    assert share >= 0.8, (g.name, name, share)
+    assert moved >= 1, (g.name, name)
+
+
+@pytest.mark.parametrize("name,model", MC.PARAMS)
+def test_matrix_family(name, model):
+    """The family builds for all eight sets: 48 targets of at most 760 codes with the boundary
+    lengths among them, N in the DNA query and targets, an asymmetric matrix; every positive
+    hit's reference path spans the window and re-scores to the brute-force score; >= 12 paths
+    have an I or a D run; >= 8 windows span two or more 256-row strips, and one, two and three
+    strips all occur."""
+    P = MC.matrix_param(name, model)
+    g = MC.matrix_family(P)
+    assert len(MC.PARAMS) == 8 and (P.sub != P.sub.T).any() and P.sub.shape[0] in (5, 24)
+    assert len(g.q) == MC.QLEN and len(g.seqs) == MC.N_TARGETS == len(g.hits)
+    lens = [len(t) for t in g.seqs]
+    assert max(lens) <= MC.MAX_TLEN and set(MC.BOUNDARY_LENS) <= set(lens)
+    assert sum(1 for kind, _ in g.meta if kind == "noise") == 4
+    if name != MC.PROTEIN:
+        assert 0.01 < float((g.q == 4).mean()) < 0.06 and any((t == 4).any() for t in g.seqs)
+    else:
+        assert g.q.max() == 23 and max(int(t.max()) for t in g.seqs if len(t)) == 23
+    live = MC.positive(g)
+    assert len(live) >= 40
+    runs, strips = 0, collections.Counter()
+    for h in live:
+        b, r, t = g.brute[h], g.refs[h], g.seqs[h]
+        s, dq, dt, cols, idn = AC.rescore(r.ops, g.q, t, b[1], b[3], P.sub, P.go, P.ge, P.model)
+        assert (s, dq, dt) == (b[0], b[2] - b[1] + 1, b[4] - b[3] + 1), (g.name, h)
+        assert (cols, idn) == (r.n_columns, r.n_identities)
+        assert r.ops[0] & 15 == AC.M and r.ops[-1] & 15 == AC.M
+        runs += any(op & 15 != AC.M for op in r.ops)
+        strips[(b[2] - b[1]) // 256 + 1] += 1
+    assert all(g.refs[h] is None for h in g.hits if h not in live)
+    assert runs >= 12, (g.name, runs)
+    assert strips[2] + strips[3] >= 8 and min(strips[1], strips[2], strips[3]) >= 1, strips
+
+
+def test_matrix_family_is_deterministic():
+    P = MC.matrix_param("asym-ncol", C.GAP_GOTOH)
+    g = MC.matrix_family(P)
+    q, seqs, meta = MC._inputs(P, MC.WINDOW, (45, 210, 480, MC.MAX_TLEN), MC.MAX_TLEN)
+    assert np.array_equal(q, g.q) and meta == g.meta
+    assert all(np.array_equal(a, b) for a, b in zip(seqs, g.seqs))
+    other = MC.matrix_family(MC.matrix_param("asym-ncol", C.GAP_MERGED))
+    assert not np.array_equal(other.q, g.q)
+
+
+@pytest.mark.parametrize("name,model", MC.PARAMS)
+def test_matrix_family_transposed(name, model):
+    """The forward mutant: a kernel that read the matrix transposed (the table of
+    tests/matrix_cases.py records the figures)."""
+    P = MC.matrix_param(name, model)
+    for mutant, sub2 in MC.forward_mutants(P.sub).items():
+        check_mutant(MC.matrix_family(P), P, mutant, sub2)

@@ -3,7 +3,8 @@ sw_align_hits_device against tests/align_cases.py).
 
 Passes A, B and C of csrc/swbank_kalign.hip run one walk in three coordinate systems, so each
 has its own strip seams, lanes and column blocks; the inputs put a live gap over every one
-(tests/test_align_cases.py proves that on the CPU).  Every record is compared with the
+(tests/test_align_cases.py proves that on the CPU); the matrix family runs the same passes under
+asymmetric matrices.  Every record is compared with the
 brute-force coordinates and, op for op, with the reference traceback of the documented path
 preference, which the preference-free check_alignment cannot see.  Every test runs with plain
 and with poisoned device buffers, through the host call (windows packed by a plan) and the
@@ -16,6 +17,7 @@ from oracle import oracle as O
 
 import align_cases as C
 import align_check as AC
+import matrix_cases as MC
 
 pytestmark = pytest.mark.gpu
 
@@ -30,8 +32,11 @@ def buffers(request):
 
 
 def _bank(P):
-    if P.letters == 20:
+    if P.sub.shape[0] > 5:
         bank = S.ScoreBank(alphabet=S.ALPHABET_PROTEIN, gap_model=P.model)
+        bank.set_matrix(P.sub, P.go, P.ge)
+    elif P.tag in MC.MATRIX_SETS:
+        bank = S.ScoreBank(gap_model=P.model)
         bank.set_matrix(P.sub, P.go, P.ge)
     else:
         bank = S.ScoreBank(gap_model=P.model)
@@ -136,6 +141,25 @@ def test_tie_rich_paths(model, mode):
     one the documented preference picks (diagonal, then D, then I; open rather than extend)."""
     for g, tag in zip(C.tie_rich_family(model), C.TIE_SETS):
         _run_group(C.dna_param(tag, model, C.TIE_SETS), g, mode)
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("name,model", MC.PARAMS)
+def test_asymmetric_matrices(name, model, mode):
+    """The matrix family of tests/matrix_cases.py (banks made with set_matrix): a kernel that
+    read the matrix transposed would change 94-98 % of these scores (tests/test_align_cases.py).
+    Coordinates against brute force, the CIGAR op for op against the reference traceback."""
+    P = MC.matrix_param(name, model)
+    assert _run_group(P, MC.matrix_family(P), mode) == 1
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("name,model", MC.PARAMS)
+def test_asymmetric_matrices_chunked(name, model, mode, monkeypatch):
+    """The same with a direction store of 1 MiB: more than one chunk."""
+    monkeypatch.setenv("SWBANK_ALIGN_MB", "1")
+    P = MC.matrix_param(name, model)
+    assert _run_group(P, MC.matrix_family(P), mode) > 1
 
 
 # ---- 2. exact CIGARs on the lane, chunk and strip edges of test_gpu_align.py ---------------

@@ -14,6 +14,7 @@ from oracle import oracle as O
 
 import align_cases as AL
 import align_check as AC
+import matrix_cases as MC
 import set_cases as SC
 
 pytestmark = pytest.mark.gpu
@@ -283,6 +284,52 @@ def test_protein_set():
         for a, qi, t in zip(dev, case.hit_queries, case.hits):
             AC.check_alignment(O, case.queries[int(qi)], case.seqs[int(t)], O.BLOSUM62, -11, -1,
                                S.GAP_GOTOH, a)
+
+
+# ---- 5b. asymmetric matrices ---------------------------------------------------------------------
+@pytest.mark.parametrize("name,model", MC.PARAMS)
+def test_asymmetric_matrix_set(name, model):
+    """The matrix family of tests/matrix_cases.py against a set of three queries (700 rows, its
+    rows 100-400, a 40-row piece) that interleave in the hit list, sentinel slots among them:
+    the host and the device form agree, and every record is the brute-force record and the
+    reference path of its (query, target), op for op.  The SET kernels build their profiles
+    per query: one built from the transposed matrix would change most of these scores."""
+    P = MC.matrix_param(name, model)
+    g = MC.matrix_family(P)
+    queries, hq, hv = MC.set_form(g)
+    case = SC.SetCase(queries, g.seqs, hq, hv, alpha=P.sub.shape[0])
+    refs = SC.pair_refs(case, P.sub, P.go, P.ge, model, f"matrix-{name}")
+    assert [h for h, r in enumerate(refs) if r is None] == sorted(MC.SET_NONE)
+    assert all(sum(1 for h, r in enumerate(refs) if r and hq[h] == i and r[0][0] > 0) >= 20
+               for i in range(3))
+    res, offs, lens = S.pack_targets(case.seqs)
+    protein = P.sub.shape[0] > 5
+    with S.ScoreBank(alphabet=S.ALPHABET_PROTEIN if protein else S.ALPHABET_DNA,
+                     gap_model=model) as bank:
+        bank.set_matrix(P.sub, P.go, P.ge)
+        bank.load_queries(queries)
+        host = bank.align_set_hits(res, offs, lens, hits=hv, hit_queries=hq)
+        assert bank.last_kernel() == f"align-set i32 nq=3 hits={len(case)} chunks=1"
+        dev = _device_set(bank, Batch(case.seqs), len(case), _stride(case), hit_queries=hq,
+                          hits=hv)
+    assert dev == host
+    seen = set()
+    for h, (a, ref) in enumerate(zip(dev, refs)):
+        if ref is None:
+            assert SC.sentinel_ok(a), (h, a)
+            continue
+        (s, qs, qe, ts, te), path = ref
+        qi, t = int(hq[h]), int(hv[h])
+        assert a.index == t and a.id == t
+        assert (a.score, a.q_start, a.q_end, a.t_start, a.t_end) == (s, qs, qe, ts, te), (h, a)
+        if s == 0:
+            assert a.flags == SC.ALIGN_EMPTY and not a.ops, (h, a)
+        else:
+            assert a.flags == 0 and tuple(a.ops) == tuple(path.ops), (h, a.cigar, path)
+            assert (a.n_columns, a.n_identities) == (path.n_columns, path.n_identities), (h, a)
+        if (qi, t) not in seen:
+            AC.check_alignment(O, queries[qi], case.seqs[t], P.sub, P.go, P.ge, model, a)
+            seen.add((qi, t))
 
 
 # ---- 6. read mapping in small ----------------------------------------------------------------------

@@ -15,6 +15,8 @@ from oracle import oracle as O
 
 import align_check as AC
 import frame_cases as F
+import matrix_cases as MC
+import seam_cases as SEAMS
 
 pytestmark = pytest.mark.gpu
 
@@ -338,7 +340,7 @@ def test_timing_brackets_translation_and_merge():
 
 # ---- 3. alignments ----------------------------------------------------------------------------------
 def _device_align(bank, bt, frames, hits, stride, hit_queries=None, hits_per_query=0, ids=None,
-                  stream=0):
+                  stream=0, table=None):
     """sw_align_frame_hits_device on torch buffers -> Alignment objects."""
     torch = _torch()
     n_hits = len(hits) if hits is not None else len(hit_queries)
@@ -356,7 +358,7 @@ def _device_align(bank, bt, frames, hits, stride, hit_queries=None, hits_per_que
         d_hit_queries=d_hq.data_ptr() if d_hq is not None else 0,
         hits_per_query=0 if d_hq is not None else hits_per_query or max(n_hits, 1),
         d_cigar=d_cig.data_ptr() if stride else 0, cigar_stride=stride,
-        d_ids=d_ids.data_ptr() if d_ids is not None else 0, stream=stream)
+        d_ids=d_ids.data_ptr() if d_ids is not None else 0, stream=stream, codon_table=table)
     bank.sync()
     rec = d_out.cpu().numpy().view(S.ALIGNMENT_DTYPE)
     cig = d_cig.cpu().numpy().view(np.uint32)
@@ -365,10 +367,10 @@ def _device_align(bank, bt, frames, hits, stride, hit_queries=None, hits_per_que
     return S.alignments_from(rec, cig)
 
 
-def _expected(bank, seqs, frames, pairs, ids=None, stride=None):
+def _expected(bank, seqs, frames, pairs, ids=None, stride=None, table=None):
     """What the frame call must return for the (query, target) pairs: align_set_hits on a batch
     holding the model's translation of each pair's frame, then the record rules."""
-    trans = [F.translate(seqs[k], int(frames[i][k])) for i, k in pairs]
+    trans = [F.translate(seqs[k], int(frames[i][k]), table) for i, k in pairs]
     res, offs, lens = S.pack_targets(trans)
     base = bank.align_set_hits(res, offs, lens, hit_queries=[i for i, _ in pairs])
     out = []
@@ -441,6 +443,66 @@ def test_chain_and_alignments_of_the_top_hits(model):
     best = {i: alns[i * k] for i in range(nq)}  # a planted query aligns end to end, no gaps
     for i in range(nq):
         assert best[i].cigar == f"{len(qs[i])}M" and best[i].n_identities == len(qs[i])
+
+
+@pytest.mark.parametrize("model", MODELS)
+@pytest.mark.parametrize("table", ["standard", "stop-x"])
+def test_asymmetric_matrix(table, model):
+    """asym-prot at -11 / -1 through the frames (tests/matrix_cases.frame_case: the transposed
+    matrix changes the frame score of 25-27 of the 27 planted targets, tests/test_frame_cases.py):
+    scores and frames against the oracle on the model's translations, device and host form;
+    align_frame_hits, host and device, on each query's 12 best hits against align_set_hits on
+    the model's translation under the record rules, the CIGAR re-scored over the translated
+    codes under the asymmetric matrix.  The custom table (two more stops, a codon for X; X and
+    * in the queries) reads rows and columns 22 / 23 of the matrix."""
+    tab = MC.stop_x_table() if table == "stop-x" else None
+    sub = SEAMS.MATRICES[MC.PROTEIN]()
+    pen = MC.MATRIX_SETS[MC.PROTEIN]
+    qs, seqs, planted = MC.frame_case(tab)
+    wsc, wfr = MC.frame_oracle(tab, model)
+    nq, k = len(qs), 12
+    bt = Batch(seqs)
+    stride = 2 * (bt.max_len // 3) + 1
+    hits = np.stack([np.argsort(-wsc[i].astype(np.int64), kind="stable")[:k] for i in range(nq)])
+    pairs = [(i, int(hits[i][j])) for i in range(nq) for j in range(k)]
+    hv = hits.reshape(-1).astype(np.uint64)
+    with S.ScoreBank(alphabet=S.ALPHABET_PROTEIN, gap_model=model) as bank:
+        bank.set_matrix(sub, *pen)
+        bank.load_queries(qs)
+        got, gfr, name = _score_device(bank, bt, nq, table=tab)
+        assert name == f"frames nq={nq} n={bt.n} slices=1"
+        bad = np.nonzero(got != wsc)
+        assert bad[0].size == 0, (bad, got[bad], wsc[bad])
+        assert np.array_equal(gfr, wfr)
+        sc, fr = bank.score_frames(bt.res, bt.offs, bt.lens, codon_table=tab)
+        assert np.array_equal(sc, wsc) and np.array_equal(fr, wfr)
+        exp, trans = _expected(bank, seqs, wfr, pairs, table=tab)
+        dev = _device_align(bank, bt, wfr, hv, stride, hits_per_query=k, table=tab)
+        assert bank.last_kernel() == f"align-frame i32 nq={nq} hits={nq * k} chunks=1"
+        host = bank.align_frame_hits(bt.res, bt.offs, bt.lens, wfr, hits=hv, hits_per_query=k,
+                                     codon_table=tab)
+    frames = {int(wfr[i][t]) for i, t in pairs}
+    assert len(frames) >= 5 and min(frames) < 3 <= max(frames)
+    gapped, windows = 0, []
+    for (i, t), a, e, hrec, tr in zip(pairs, dev, exp, host, trans):
+        f, L = int(wfr[i][t]), len(seqs[t])
+        assert a == e == hrec, ((i, t), a, e, hrec)
+        assert (a.index, a.score, a.frame) == (t, int(wsc[i][t]), f)
+        assert a.flags == F.frame_flags(f) and a.has_path and 0 <= a.t_start <= a.t_end < L
+        o = f % 3
+        a_start = (a.t_start - o) // 3 if f < 3 else (L - 1 - a.t_end - o) // 3
+        a_end = (a.t_end - o - 2) // 3 if f < 3 else (L - 1 - a.t_start - o - 2) // 3
+        assert F.nt_coords(a_start, a_end, f, L) == (a.t_start, a.t_end)
+        s, dq, dt, cols, idn = AC.rescore(a.ops, qs[i], tr, a.q_start, a_start, sub, *pen, model)
+        assert (s, dq, dt) == (a.score, a.q_end - a.q_start + 1, a_end - a_start + 1)
+        assert (cols, idn) == (a.n_columns, a.n_identities)
+        gapped += len(a.ops) > 1
+        windows.append((qs[i][a.q_start:a.q_end + 1], tr[a_start:a_end + 1]))
+    assert gapped >= 4
+    if tab is not None:  # X and * lie inside the aligned windows, on either side
+        for side in (0, 1):
+            codes = np.concatenate([w[side] for w in windows])
+            assert (codes == F.X).any() and (codes == F.STOP).any()
 
 
 @pytest.mark.parametrize("form", ["host", "device"])

@@ -13,6 +13,8 @@ import swbank as S
 from oracle import oracle as O
 
 import align_cases as C
+import align_check as AC
+import matrix_cases as MC
 import strand_cases as SC
 
 pytestmark = pytest.mark.gpu
@@ -439,6 +441,45 @@ def test_tie_rich_paths_on_the_reverse_strand(model, mode):
         _run_group(C.dna_param(tag, model, C.TIE_SETS), g, mode)
 
 
+def _matrix_bank(P):
+    bank = S.ScoreBank(gap_model=P.model)
+    bank.set_matrix(P.sub, P.go, P.ge)
+    return bank
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("name,model", MC.DNA_PARAMS)
+def test_asymmetric_matrices_on_alternating_strands(name, model, mode):
+    """The matrix family of tests/matrix_cases.py, forward hits on t and reverse hits on the
+    stored rc(t) by turns.  A reverse hit is walked under smat'[q][c] = smat[q][comp c]: built
+    from the uncomplemented matrix, with the rows complemented, from the transposed matrix or
+    with both sides complemented it would change 94-100 % of these scores
+    (tests/test_strand_cases.py), which no match / mismatch table shows for the second and
+    third.  Records equal the flipped references op for op, and a reverse hit's counts are
+    recomputed from its ops on the reverse complement of the stored target."""
+    P = MC.matrix_param(name, model)
+    g = MC.matrix_family(P)
+    stored, strands = MC.strand_form(g)
+    with _matrix_bank(P) as bank:
+        bank.load_query(g.q)
+        alns = _align(bank, mode, stored, g.hits, strands)
+    assert len(alns) == len(g.hits)
+    gapped = 0
+    for h, a in zip(g.hits, alns):
+        want, L = _expect(g, h), len(stored[h])
+        if strands[h]:
+            want = SC.flip_record(want, L)
+        assert a == want, (g.name, h, a, want)
+        assert a.reverse == bool(strands[h])
+        if strands[h] and a.score > 0:
+            s, dq, dt, cols, idn = AC.rescore(a.ops, g.q, SC.revcomp(stored[h]), a.q_start,
+                                              L - 1 - a.t_end, P.sub, P.go, P.ge, P.model)
+            assert (s, dq, dt) == (a.score, a.q_end - a.q_start + 1, a.t_end - a.t_start + 1)
+            assert (cols, idn) == (a.n_columns, a.n_identities), (h, a)
+            gapped += len(a.ops) > 1
+    assert gapped >= 6
+
+
 def _set_case():
     """Three queries, 40 targets (every third one reverse-complemented, N codes, an empty one),
     the oracle's strand matrix, and per (query, target) the forward call's expectation on the
@@ -547,6 +588,77 @@ def test_null_strands_equal_the_set_call_byte_for_byte(model):
         _, rec0, cig0 = _device_align(bank, seqs, hv, np.zeros((3, n), np.uint8), stride,
                                       hits_per_query=n)
     assert rec0.tobytes() == rec.tobytes() and cig0.tobytes() == cig.tobytes()
+
+
+@pytest.mark.parametrize("model", C.MODELS)
+def test_null_strands_equal_the_set_call_under_an_asymmetric_matrix(model):
+    """asym-ncol (a non-uniform N column, a positive N x N score): the matrix family against a
+    set of three queries in the [nq, k] layout, a sentinel among the hits."""
+    torch = _torch()
+    P = MC.matrix_param("asym-ncol", model)
+    g = MC.matrix_family(P)
+    qs = MC.set_form(g)[0]
+    n = len(g.seqs)
+    hv = np.tile(np.arange(n, dtype=np.uint64), 3)
+    hv[5] = S.HIT_NONE
+    stride = 2 * MC.MAX_TLEN + 1
+    with _matrix_bank(P) as bank:
+        bank.load_queries(qs)
+        alns, rec, cig = _device_align(bank, g.seqs, hv, None, stride, hits_per_query=n)
+        assert bank.last_kernel().startswith("align-strand i32 nq=3")
+        bt = Batch(g.seqs)
+        d_hits = _to_dev(hv)
+        d_out = _filled(len(hv) * S.ALIGNMENT_DTYPE.itemsize)
+        d_cig = torch.full((len(hv) * stride,), 0x3C3C3C3C, dtype=torch.int32,
+                           device=torch.device("cuda", 0))
+        torch.cuda.synchronize()
+        bank.align_set_hits_device(*bt.ptrs(), bt.n, bt.max_len, len(hv), d_out.data_ptr(),
+                                   d_hits=d_hits.data_ptr(), hits_per_query=n,
+                                   d_cigar=d_cig.data_ptr(), cigar_stride=stride)
+        bank.sync()
+        assert d_out.cpu().numpy().tobytes() == rec.tobytes()
+        assert d_cig.cpu().numpy().tobytes() == cig.tobytes()
+        res, offs, lens = S.pack_targets(g.seqs)
+        assert bank.align_strand_hits(res, offs, lens, hits=hv, hits_per_query=n) == \
+            bank.align_set_hits(res, offs, lens, hits=hv, hits_per_query=n)
+    for h in g.hits:  # row 0 is the family's own query: its records are the family's
+        assert h == 5 or alns[h] == _expect(g, h), (h, alns[h])
+    assert sum(1 for a in alns if len(a.ops) > 1) >= 30
+
+
+# ---- 3b. the first-column rule on the reverse strand ----------------------------------------------
+def test_first_column_rule_on_the_reverse_strand():
+    """Merged 3 / -3 / -1 / -1 (max(s) > open + extend): the one rule that is not
+    reversal-symmetric.  On a reverse hit the first column is the stored target's last code; on
+    7 of the 24 reverse hits of tests/matrix_cases.col0_family the rule applied at the other end
+    gives another score (tests/test_strand_cases.py).  Scores and strands against the oracle on
+    rc(target): the device form with the bank's own complement and with a resident one, and
+    the host form.  The alignment entries refuse these penalties (include/swbank.h: the start
+    rule has no reversed problem), so the strand alignments have nothing to return."""
+    g = MC.col0_family()
+    P = MC.col0_param()
+    pen = (3, -3, P.go, P.ge)
+    stored, strands = MC.strand_form(g)
+    wsc, wst, fwd, rev = _want([g.q], stored, pen, P.model)
+    assert int(wst[0][strands == 1].sum()) >= 18
+    bt = Batch(stored)
+    with _bank(pen, P.model) as bank:
+        bank.load_query(g.q)
+        got, gst, name = _score_device(bank, bt, 1)
+        assert name == f"strands nq=1 n={bt.n} slices=1"
+        bad = np.nonzero(got[0] != wsc[0])[0]
+        assert bad.size == 0, (bad, got[0][bad], wsc[0][bad], fwd[0][bad], rev[0][bad])
+        assert np.array_equal(gst, wst)
+        d_rc = _resident_rc(bank, bt)
+        got2, gst2, _ = _score_device(bank, bt, 1, d_rc=d_rc.data_ptr())
+        assert np.array_equal(got2, wsc) and np.array_equal(gst2, wst)
+        sc, st = bank.score_strands(bt.res, bt.offs, bt.lens)
+        assert np.array_equal(sc, wsc[0]) and np.array_equal(st, wst[0])
+        hv = np.arange(bt.n, dtype=np.uint64)
+        with pytest.raises(S.SwbankError) as ei:
+            bank.align_strand_hits(bt.res, bt.offs, bt.lens, strands=wst, hits=hv,
+                                   hits_per_query=bt.n)
+        assert ei.value.status == S.ERR_UNSUPPORTED
 
 
 def test_coordinates_only_and_short_cigar_space():

@@ -12,7 +12,9 @@ from oracle import oracle as O
 
 import align_cases as C
 import align_check as AC
+import matrix_cases as MC
 import strand_cases as SC
+from test_align_cases import check_mutant
 
 SUB = O.dna_matrix(SC.REF[0], SC.REF[1])
 MODELS = [O.GAP_MERGED, O.GAP_GOTOH]
@@ -129,3 +131,84 @@ def test_flip_record():
     e = S.Alignment(0, 0, 0, S.ALIGN_EMPTY, 0, 0, 0, 0, 0, 0)
     f = SC.flip_record(e, 0)
     assert (f.flags, f.t_start, f.t_end, f.empty, f.reverse) == (S.ALIGN_EMPTY | 8, 0, 0, True, True)
+
+
+# ---- asymmetric matrices and the first-column rule on the reverse strand --------------------------
+def test_reverse_mutants_are_what_they_say():
+    """On a stored code c = comp(t) the right smat'[q][c] = sub[q][comp c] gives sub[q][t]; the
+    four wrong ones are different matrices under every asymmetric DNA matrix; under a match /
+    mismatch table the complemented rows and the transposed matrix are the right matrix (no test
+    built on set_penalties can see them), the other two amount to a missing complement."""
+    for name in ("asym-pair", "asym-ncol", "asym-odd"):
+        sub = MC.matrix_param(name, O.GAP_GOTOH).sub
+        muts = MC.reverse_mutants(sub)
+        assert sorted(muts) == ["both-sides", "no-complement", "rows", "transposed"]
+        assert all((m != sub).any() for m in muts.values())
+        assert np.array_equal(muts["transposed"], sub.T)
+        assert np.array_equal(muts["no-complement"], sub[:, MC.COMP])
+    hidden = MC.reverse_mutants(SUB)
+    assert all(np.array_equal(hidden[k], SUB) for k in ("rows", "transposed"))
+    assert np.array_equal(hidden["both-sides"], hidden["no-complement"])
+    assert (hidden["no-complement"] != SUB).any()
+
+
+@pytest.mark.parametrize("name,model", MC.DNA_PARAMS)
+def test_matrix_family_reverse_mutants(name, model):
+    """A strand kernel that built smat' from the matrix uncomplemented, with the rows
+    complemented, from the transposed matrix or with both sides complemented: each changes the
+    score of >= 80 % of the family's positive hits and at least one record (the table of
+    tests/matrix_cases.py records the figures)."""
+    P = MC.matrix_param(name, model)
+    g = MC.matrix_family(P)
+    for mutant, sub2 in MC.reverse_mutants(P.sub).items():
+        check_mutant(g, P, "reverse " + mutant, sub2)
+
+
+def test_strand_form_alternates_and_flips_back():
+    g = MC.matrix_family(MC.matrix_param("asym-ncol", O.GAP_MERGED))
+    stored, strands = MC.strand_form(g)
+    assert strands.tolist() == [k % 2 for k in range(len(g.seqs))]
+    assert any((t == 4).any() for t, s in zip(stored, strands) if s)
+    for t, s, st in zip(g.seqs, stored, strands):
+        assert np.array_equal(SC.revcomp(s) if st else s, t)
+    rev = [h for h in MC.positive(g) if strands[h]]
+    assert len(rev) >= 20
+    for h in rev:  # the flipped coordinates are those of brute force on the stored target's rc
+        e = SC.flip_ends(g.brute[h], len(stored[h]))
+        assert (e[3], e[4]) == (len(stored[h]) - 1 - g.brute[h][4], len(stored[h]) - 1 - g.brute[h][3])
+
+
+def test_col0_family():
+    """Merged 3 / -3 / -1 / -1 (max(s) > open + extend): of the reverse hits of the strand form
+    at least a quarter have an alignment that must use the reverse target's first column (the
+    stored target's last code: leaving it out lowers the score), and on at least a quarter the
+    first-column rule is alive: applying it at the other end of the target (which is what
+    scoring rc(query) against the stored target amounts to) gives another score."""
+    g = MC.col0_family()
+    P = MC.col0_param()
+    assert P.model == O.GAP_MERGED and int(P.sub.max()) > -(P.go + P.ge)
+    kinds, want, mirror, touches = g.meta
+    lens = [len(t) for t in g.seqs]
+    assert max(lens) <= 200 and set(MC.BOUNDARY_LENS) <= set(lens) and len(g.seqs) == 48
+    stored, strands = MC.strand_form(g)
+    fwd, rev = SC.oracle_strands(g.q, stored, (3, -3, P.go, P.ge), P.model)
+    best, strand = SC.merge(fwd, rev)
+    hits = strands == 1
+    assert np.array_equal(rev[hits], want[hits]) and np.array_equal(fwd[~hits], want[~hits])
+    n = int(hits.sum())
+    assert n == 24 and int(strand[hits].sum()) >= 18  # the reverse strand wins where it should
+    alive = hits & (want != mirror)
+    print(f"\n    col0: {int((touches & hits).sum())} of {n} reverse hits need the first column, "
+          f"the rule is alive on {int(alive.sum())}", end="")
+    assert 4 * int((touches & hits).sum()) >= n and 4 * int(alive.sum()) >= n
+
+
+def test_col0_has_no_reversed_start():
+    """Why the col0 family carries scores only: include/swbank.h defines an alignment's start by
+    the end rule on the reversed prefixes, and under the first-column rule the reversed
+    prefixes of some pairs do not score what the pair scores (brute_ends_batch asserts that
+    they do).  The alignment entries refuse these penalties (SW_ERR_UNSUPPORTED; the GPU
+    tests' refusals), so there is no record to expect."""
+    g = MC.col0_family()
+    with pytest.raises(AssertionError, match="reversed prefixes"):
+        C.brute_batch(g.q, g.seqs, MC.col0_param())
