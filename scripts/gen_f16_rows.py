@@ -43,7 +43,8 @@ the DNA letter-pair table, without a table per letter pair.
 
 Skewed merged pair rows (SWK_F16SKEW_F/M/L, skew_pair_block below): cells in anti-diagonal
 frames that restart every 8 rows, 4.75 VALU per row with the letter-pair table holding s + 2e
-(s + 2e - 8e in a block's first row).
+(s + 2e - 8e in a block's first row); SWK_F16SKEW8_F/L: the same rows with the running best in
+eight accumulators named by frame mod 8, one move per column, 4.66 per row.
 
 No two dependent packed (VOP3P) ops are adjacent (gfx950 needs a wait state between them;
 v_perm_b32 -> VOP3P needs none), so a block needs no s_nop inside; LLVM adds one wait state
@@ -153,7 +154,8 @@ def pair_gotoh_block(first, last, nrows=8):
     return out + gotoh_block("pair", last, nrows)
 
 
-SKEW_ACC = 4  # accumulators of the running best (csrc: SWK_SKEW_ACC)
+SKEW_ACC = 8       # accumulators of the running best (csrc: SWK_SKEW_ACC)
+SKEW_ACC_TRIM = 4  # ... of the trimmed kernel, which leaves a chunk at any column (SWK_SKEW_ACC_TRIM)
 
 
 def _regs(ln):
@@ -172,7 +174,7 @@ def check_no_adjacent_dependence(lines):
     return lines
 
 
-def skew_pair_block(kind, nrows=8):
+def skew_pair_block(kind, nacc=SKEW_ACC_TRIM, nrows=8):
     """Pair-profile block in block frames (DNA, merged gaps, DESIGN 3.1 "skewed rows"): cell
     (i, j) is held with the offset c_f = e (f - 1), f = (i mod 8) + j, so the gap extension is
     paid by the frame and a row is 4 VALU:
@@ -195,8 +197,19 @@ def skew_pair_block(kind, nrows=8):
     of column j).  The folds go into the last block, between the rows' dependent pairs; the
     last accumulator's move and class 7 (row 7 of the last block ends the column) into the
     first block of the next column, before it overwrites row 7: x, y, z = rows 15, 23, 31.
-    16 max3 and 4 adds per column: 4.75 VALU per row with the 4 shifts."""
-    assert nrows == 8 and SKEW_ACC == 4
+    16 max3 and 4 adds per column: 4.75 VALU per row with the 4 shifts.
+
+    nacc = 8 (SWK_F16SKEW8_F / _L; the middle blocks are the same): one accumulator per frame,
+    named by the frame mod 8, so the accumulator of class u in column j is b[(u + j) mod 8] and
+    stays with its frame from column to column.  Frame j leaves after column j and its
+    accumulator takes frame j + 8, class 7 of column j + 1: one + 8e move per column (- 8e
+    negated by the instruction's modifiers), run with class 7's delayed fold in the next first
+    block.  The text is the same for every column: the caller binds the operands by class,
+    %[b0] .. %[b6] = the accumulators of classes 0-6 of this column (b[(u + jj) mod 8]), %[bf]
+    = the one of the previous column's class 7 (b[(jj + 6) mod 8]), %[bm] = the one that moves
+    (b[(jj + 7) mod 8], the previous column's class 0); after the 8 columns of a chunk the
+    names are back where they were.  16 max3 and 1 add per column."""
+    assert nrows == 8 and nacc in (4, 8)
     rows = []  # per row: [nd, tt, ao, hh]
     for i in range(nrows):
         dcur, dnext = ("%[Da]", "%[Db]") if i % 2 == 0 else ("%[Db]", "%[Da]")
@@ -207,12 +220,15 @@ def skew_pair_block(kind, nrows=8):
                      f"v_pk_maximum3_f16 %[h{i}], %[t{i}], {dcur}, %[c{i}]"])
     shift = f"v_pk_add_f16 %[Db], %[t{nrows - 1}], %[ne8]"
     if kind == "F":
+        bf = "%[b3]" if nacc == 4 else "%[bf]"
+        move = ("v_pk_add_f16 %[b3], %[b3], %[e1]" if nacc == 4 else
+                "v_pk_add_f16 %[bm], %[bm], %[ne8] neg_lo:[0,1] neg_hi:[0,1]")
         nd, tt, ao, hh = rows[0]
         out = ["v_pk_add_f16 %[Da], %[dg], %[pw]", "v_pk_add_f16 %[up], %[up], %[ne8]", nd,
-               "v_pk_add_f16 %[AO], %[Da], %[no]", "v_pk_add_f16 %[b3], %[b3], %[e1]", tt, ao,
-               "v_pk_maximum3_f16 %[b3], %[b3], %[h7], %[x]", hh]
+               "v_pk_add_f16 %[AO], %[Da], %[no]", move, tt, ao,
+               f"v_pk_maximum3_f16 {bf}, {bf}, %[h7], %[x]", hh]
         nd, tt, ao, hh = rows[1]
-        out += [nd, tt, "v_pk_maximum3_f16 %[b3], %[b3], %[y], %[z]", ao, hh]
+        out += [nd, tt, f"v_pk_maximum3_f16 {bf}, {bf}, %[y], %[z]", ao, hh]
         for r in rows[2:]:
             out += r
         return check_no_adjacent_dependence(out + [shift])
@@ -228,15 +244,16 @@ def skew_pair_block(kind, nrows=8):
     base += [rows[-1][1], rows[-1][3]]  # the column's last row has no successor
     # the folds: per accumulator a chain; (line, the row of this block it waits for or None)
     chains = []
-    for a in range(SKEW_ACC):
-        u, v, b = 2 * a, 2 * a + 1, f"%[b{a}]"
+    for a in range(nacc if nacc == 4 else nrows - 1):
+        u, v, b = (2 * a, 2 * a + 1, f"%[b{a}]") if nacc == 4 else (a, None, f"%[b{a}]")
         ch = [(f"v_pk_maximum3_f16 {b}, {b}, %[g{u}], %[k{u}]", None),
               (f"v_pk_maximum3_f16 {b}, {b}, %[m{u}], %[h{u}]", u)]
-        if a < SKEW_ACC - 1:
+        if nacc == 4 and a < nacc - 1:
             ch += [(f"v_pk_add_f16 {b}, {b}, %[e1]", None),
                    (f"v_pk_maximum3_f16 {b}, {b}, %[g{v}], %[k{v}]", None),
                    (f"v_pk_maximum3_f16 {b}, {b}, %[m{v}], %[h{v}]", v)]
         chains.append(ch)
+    nch = len(chains)
     out, done = [], set()  # done: rows of this block whose H^ is written
     turn = 0
     for ln in base:
@@ -244,14 +261,14 @@ def skew_pair_block(kind, nrows=8):
         d = _regs(ln)[0]
         if ln.startswith("v_pk_maximum3") and d.startswith("%[h"):
             done.add(int(d[3:-1]))
-        for k in range(SKEW_ACC):  # one fold after each row instruction, accumulators in turn
-            ch = chains[(turn + k) % SKEW_ACC]
+        for k in range(nch):  # one fold after each row instruction, accumulators in turn
+            ch = chains[(turn + k) % nch]
             if not ch:
                 continue
             f, wait = ch[0]
             if (wait is None or wait in done) and _regs(out[-1])[0] not in _regs(f)[1]:
                 out.append(ch.pop(0)[0])
-                turn = (turn + k + 1) % SKEW_ACC
+                turn = (turn + k + 1) % nch
                 break
     assert not any(chains), chains
     return check_no_adjacent_dependence(out)
@@ -290,6 +307,9 @@ def main():
     parts.append("#define SWK_F16PAIRG_L \\\n" + fmt(pair_gotoh_block(False, True)))
     for kind in "FML":
         parts.append(f"#define SWK_F16SKEW_{kind} \\\n" + fmt(skew_pair_block(kind)))
+    for kind in "FL":  # (the middle blocks hold nothing of the best)
+        parts.append(f"#define SWK_F16SKEW8_{kind} \\\n" +
+                     fmt(skew_pair_block(kind, SKEW_ACC)))
     # mode F (profile words {s, 1.0}: one packed FMA per row, no lookup), 8-row blocks
     for last in (0, 1):
         parts.append(f"#define SWK_F16M_F_Z0_L{last} \\\n" + fmt(merged_block("F", 0, last)))

@@ -71,9 +71,12 @@ static inline int swk_wbal_admissible(unsigned long long U, unsigned long long B
 }
 
 /* Accumulators of the running best in the skewed rows of the tile kernel (the
- * generator's SKEW_ACC), and the words per lane of a wave's balanced hand-off state: H^ and T~
- * of R rows, the diagonal above, the accumulators (the unskewed rows have one best). */
-#define SWK_SKEW_ACC 4
+ * generator's SKEW_ACC: one per frame mod 8; SKEW_ACC_TRIM for the trimmed kernel), and the
+ * words per lane of a wave's balanced hand-off state: H^ and T~ of R rows, the diagonal above,
+ * the accumulators (the unskewed rows have one best).  The host sizes the state for the larger
+ * count. */
+#define SWK_SKEW_ACC 8
+#define SWK_SKEW_ACC_TRIM 4
 #define SWK_BAL_WORDS(R, ACC) (2 * (R) + 1 + (ACC))
 
 /* Kinds of a launch's fault marks (cross-workgroup hand-off waits that ran out).  Each kind has

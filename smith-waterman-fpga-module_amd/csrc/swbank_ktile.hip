@@ -8,9 +8,21 @@ namespace swk {
 // opaque copy of the lane at each call.  __shfl_xor's addresses depend on the lane alone, LLVM
 // hoists them out of the phase loop (3 VGPRs for the steps DPP cannot do), and the skewed column
 // has none to spare.
+// ulen != 0: the caller has declared every target ulen codes long (a uniform batch), so a tile's
+// counts are the batch's, scalar, without the reduction over the lanes; a tile past the batch's
+// end holds no target (one empty chunk, no full loads), as the reduction finds it.
 template <int C>
 __device__ __forceinline__ void tile_chunks_local(const Lane2& t, size_t tlo, size_t thi, size_t n,
-                                                  int lane, int& nch, int& nfull, int& ncl) {
+                                                  int lane, int& nch, int& nfull, int& ncl,
+                                                  int tile, uint32_t ulen) {
+  if (ulen) {
+    const bool any = (size_t)tile * SWB_TILE < n;
+    const int lx = any ? (int)ulen : 0;
+    nch = max(1, (lx + C - 1) / C);
+    ncl = lx == 0 ? C : lx - C * (nch - 1);
+    nfull = lx / C;
+    return;
+  }
   uint32_t Lmax = max(t.llo, t.lhi);
   uint32_t Lmin = min(tlo < n ? t.llo : ~0u, thi < n ? t.lhi : ~0u);
   uint32_t ol = (uint32_t)lane;
@@ -39,7 +51,7 @@ __device__ __forceinline__ void tile_chunks_local(const Lane2& t, size_t tlo, si
 // exits are out of line (1,458)
 template <int R, int RB, bool COL0, bool PROF, bool GOTOH, bool F16, bool PAIR = false,
           bool MQ = false, bool STREAM = false, int C = 8, bool BAL = false, bool TRIM = false,
-          bool SKEW = false>
+          bool SKEW = false, int NB = SKEW ? (TRIM ? SWK_SKEW_ACC_TRIM : SWK_SKEW_ACC) : 1>
 __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const ScoreArgs a) {
   static_assert(!BAL || (!MQ && !STREAM && !COL0), "balanced ranges: one query, resident batch");
   static_assert(!TRIM || (BAL && PAIR), "trimmed last chunks: the balanced pair kernel");
@@ -223,7 +235,7 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
   int nch, nfull, ncl;
   if constexpr (SKEW)
     tile_chunks_local<C>(cur, (size_t)tile * SWB_TILE + lane, (size_t)tile * SWB_TILE + lane + 64,
-                         n, lane, nch, nfull, ncl);
+                         n, lane, nch, nfull, ncl, tile, TRIM ? 0u : a.ulen);
   else
     tile_chunks<C>(cur, (size_t)tile * SWB_TILE + lane, (size_t)tile * SWB_TILE + lane + 64, n,
                    nch, nfull, ncl);
@@ -243,19 +255,23 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
   // mod 8) + (tile column j), the anti-diagonal within a block of 8 rows: H^ = H + c_k, T~ = G +
   // c_k, c_k = e (k - 1); every wave has the same frames.  ct[k + 2] = c_k (both halves), read
   // with scalar loads; row -1 and column -1 hold H = 0 as their frames' floors and a T~ far below
-  // every floor (-2048: it only ever enters a max).  The running best is SWK_SKEW_ACC
-  // accumulators: bk[a] folds the rows r with (r mod 8) / 2 = a (gen_f16_rows.py)
+  // every floor (-2048: it only ever enters a max).  The running best is NB accumulators
+  // (gen_f16_rows.py): 8, bk[f mod 8] folds the rows in frame f and takes frame f + 8 when f
+  // leaves the column, one move per column, the names back in place after a chunk's 8 columns;
+  // or 4 (the trimmed kernel, whose tile end meets a chunk at any column): bk[a] folds the rows r
+  // with (r mod 8) / 2 = a, one move per column each
   typedef __attribute__((address_space(4))) const uint32_t cst_u32;
   cst_u32* const ct = reinterpret_cast<cst_u32*>(reinterpret_cast<uintptr_t>(a.ctab));
   constexpr uint32_t SKEW_NEG = 0xBC00BC00u;
-  constexpr int NB = SKEW ? SWK_SKEW_ACC : 1;
-  static_assert(NB == 1 || NB == 4, "the generated rows fold into 4 accumulators");
+  static_assert(SKEW ? (NB == 4 || (NB == 8 && !TRIM)) : NB == 1,
+                "the generated rows fold into 4 accumulators, or 8 renamed over a whole chunk");
   uint32_t skew_c0 = 0;  // c of a block's row 0 in column -1 (frame -1)
   if constexpr (SKEW) skew_c0 = ct[1];
   // a tile's column -1: H = 0 in every row's frame (Hl[r] = c_{(r mod 8) - 1}), the diagonal
   // above the wave's row 0 (row 7 of the block above: frame 6), and each accumulator at the floor
   // of the frame it starts column 0 in (frame 2a; the last one a move before it, frame 5, since
-  // column 0's first block runs that move and folds column -1's class 7)
+  // column 0's first block runs that move and folds column -1's class 7; of 8: bk[n] at the
+  // floor of frame n, bk[7] a move before it, frame -1)
   const auto skew_reset = [&](u16x2 (&H)[R], u16x2 (&X)[R], u16x2 (&bk)[NB], u16x2& pup) {
     // (from an opaque copy: the values are loop-invariant, and LLVM would otherwise keep
     // them live across the column loop, spilled)
@@ -279,14 +295,22 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
       bk[1] = H[3];
       bk[2] = H[5];
       bk[3] = H[6];
+    } else if constexpr (NB == 8) {
+#pragma unroll
+      for (int i = 0; i < 7; ++i) bk[i] = H[i + 1];
+      bk[7] = H[0];
     }
   };
   (void)ct; (void)skew_reset;
   if (wave == 0) {
     // (entry 64 of the first ring slot's C rows: no lane's own entry, so no wave overwrites it)
+    // (SKEW: T~ = -2048 once, here; the floor beside it changes with the column and is
+    // rewritten in every chunk-phase.  The trimmed kernel, a ragged batch's, is kept as it was
+    // measured: it rewrites both words)
     if (lane < C)
-      ring[lane * RS + 64] = F16 ? make_uint2(0u, GOTOH ? 0u : as_u32(as_u16x2(NOE2)))
-                                 : make_uint2(S | (S << 16), 0u);
+      ring[lane * RS + 64] = SKEW && !TRIM ? make_uint2(0u, SKEW_NEG)
+                             : F16 ? make_uint2(0u, GOTOH ? 0u : as_u32(as_u16x2(NOE2)))
+                                   : make_uint2(S | (S << 16), 0u);
     if (seg_in)  // the previous segment's bottom row of chunk 0
       dma_edge_chunk<C>(a.edge_in + (size_t)(MQ ? unit : tile) * a.ecols * 64, ein, lane);
   }
@@ -531,7 +555,8 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
                                   a.ustride);
         if constexpr (SKEW)
           tile_chunks_local<C>(cur, (size_t)ntile * SWB_TILE + lane,
-                               (size_t)ntile * SWB_TILE + lane + 64, n, lane, nch_n, nfull_n, ncl_n);
+                               (size_t)ntile * SWB_TILE + lane + 64, n, lane, nch_n, nfull_n, ncl_n,
+                               ntile, TRIM ? 0u : a.ulen);
         else
           tile_chunks<C>(cur, (size_t)ntile * SWB_TILE + lane,
                          (size_t)ntile * SWB_TILE + lane + 64, n, nch_n, nfull_n, ncl_n);
@@ -561,8 +586,9 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
       // SKEW: the floors of this chunk-phase's frames, cs[s] = c_k for k = 8 c + s (row r of
       // column jj: s = (r mod 8) + jj), the same for every wave, read into SGPRs.  Wave 0 has no
       // wave above it: its row -1 holds H = 0 in the frame of a block's row 7, which moves with
-      // the column, so it rewrites the boundary entries of the 8 column rows before it reads
-      // them (the same wave's LDS accesses stay in order).  Their T~ = -2048 becomes -2048 - 8e
+      // the column, so it rewrites the floors of the boundary entries of the 8 column rows before
+      // it reads them (the same wave's LDS accesses stay in order; the T~ word beside each was
+      // written once, at the kernel's start).  Their T~ = -2048 becomes -2048 - 8e
       // by the shift of row 0: exact (a multiple of 8 above -4096) and below A - o >= -2048,
       // beside which alone it enters a max
       const int cu = __builtin_amdgcn_readfirstlane(c);
@@ -573,7 +599,16 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
         for (int s = 0; s < 7 + C; ++s) cs[s] = sl[s];
         if (wave == 0 && lane == 0) {
 #pragma unroll
-          for (int jj = 0; jj < C; ++jj) ring[jj * RS + 64] = make_uint2(cs[jj + 7], SKEW_NEG);
+          // (relaxed atomic stores: LLVM otherwise pairs them into ds_write2_b32, whose 8-bit
+          // offsets need an address add per pair; single stores take the row's offset as it is)
+          for (int jj = 0; jj < C; ++jj) {
+            if constexpr (TRIM)
+              ring[jj * RS + 64] = make_uint2(cs[jj + 7], SKEW_NEG);
+            else
+              __atomic_store_n(reinterpret_cast<__attribute__((address_space(3))) uint32_t*>(
+                                   (size_t)(lds_void_ptr)&ring[jj * RS + 64].x),
+                               cs[jj + 7], __ATOMIC_RELAXED);
+          }
         }
       }
       (void)cu; (void)cs;
@@ -648,7 +683,8 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
             column_merged<R, RB, false>(lk, diag, upX, Hl, Xl, best, S2, O2, E2);
           }
         } else if constexpr (PAIR && SKEW) {
-          // the skewed rows (scripts/gen_f16_rows.py, skew_pair_block): 4.75 VALU per row; the
+          // the skewed rows (scripts/gen_f16_rows.py, skew_pair_block): 4.66 VALU per row (4.75
+          // with the trimmed kernel's four accumulators); the
           // table words hold s + 2e (a block's first row: s + 2e - 8e), row r's floor is
           // cs[(r mod 8) + jj]; the folds of the best sit in the last block, the last
           // accumulator's second half in the next column's first block
@@ -657,6 +693,7 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
           const int nsh = jj + 1 < C ? 8 * ((jj + 1) & 3) : 0;
           uint32_t Da, Db, AO;
           const uint32_t no = as_u32(as_u16x2(NO2)), e1 = a.f16_e1, ne8 = a.f16_ne8;
+          (void)e1;
 #define SWK_SKEW_OUT(B, DA, DB)                                                               \
   [h0] "+v"(Hl[B]), [h1] "+v"(Hl[B + 1]), [h2] "+v"(Hl[B + 2]), [h3] "+v"(Hl[B + 3]),          \
       [h4] "+v"(Hl[B + 4]), [h5] "+v"(Hl[B + 5]), [h6] "+v"(Hl[B + 6]), [h7] "+v"(Hl[B + 7]),  \
@@ -676,10 +713,18 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
           // (the table words one block ahead, as in the unskewed column below)
           uint4 pB0 = ld4(acur + 48), pB1 = ld4(acur + 64);  // block 1
           __builtin_amdgcn_sched_barrier(0);
-          asm volatile(SWK_F16SKEW_F
-                       : SWK_SKEW_OUT(0, "=&v", "=&v"), [up] "+v"(upX), [b3] "+v"(bk[3])
-                       : SWK_SKEW_IN(pA0, pA1), [e1] "s"(e1), [dg] "v"(diag), [pw] "v"(pw),
-                         [x] "v"(Hl[15]), [y] "v"(Hl[23]), [z] "v"(Hl[31]));
+          // (NB == 8: the accumulators by class, bk[(u + jj) mod 8], see the generator)
+          if constexpr (NB == 8)
+            asm volatile(SWK_F16SKEW8_F
+                         : SWK_SKEW_OUT(0, "=&v", "=&v"), [up] "+v"(upX),
+                           [bf] "+v"(bk[(jj + 6) & 7]), [bm] "+v"(bk[(jj + 7) & 7])
+                         : SWK_SKEW_IN(pA0, pA1), [dg] "v"(diag), [pw] "v"(pw),
+                           [x] "v"(Hl[15]), [y] "v"(Hl[23]), [z] "v"(Hl[31]));
+          else
+            asm volatile(SWK_F16SKEW_F
+                         : SWK_SKEW_OUT(0, "=&v", "=&v"), [up] "+v"(upX), [b3] "+v"(bk[3 % NB])
+                         : SWK_SKEW_IN(pA0, pA1), [e1] "s"(e1), [dg] "v"(diag), [pw] "v"(pw),
+                           [x] "v"(Hl[15]), [y] "v"(Hl[23]), [z] "v"(Hl[31]));
           pA0 = ld4(acur + 80);  // block 2
           pA1 = ld4(acur + 96);
           __builtin_amdgcn_sched_barrier(0);
@@ -693,11 +738,20 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
           pA1 = ld4(acur + 32);
           pw = ld1(acur + 12);
           __builtin_amdgcn_sched_barrier(0);
-          asm volatile(SWK_F16SKEW_L
-                       : SWK_SKEW_OUT(R - 8, "+v", "+v"), [b0] "+v"(bk[0]), [b1] "+v"(bk[1]),
-                         [b2] "+v"(bk[2]), [b3] "+v"(bk[3])
-                       : SWK_SKEW_IN(pB0, pB1), [e1] "s"(e1), SWK_SKEW_FOLD(g, 0),
-                         SWK_SKEW_FOLD(k, 8), SWK_SKEW_FOLD(m, 16));
+          if constexpr (NB == 8)
+            asm volatile(SWK_F16SKEW8_L
+                         : SWK_SKEW_OUT(R - 8, "+v", "+v"), [b0] "+v"(bk[jj & 7]),
+                           [b1] "+v"(bk[(jj + 1) & 7]), [b2] "+v"(bk[(jj + 2) & 7]),
+                           [b3] "+v"(bk[(jj + 3) & 7]), [b4] "+v"(bk[(jj + 4) & 7]),
+                           [b5] "+v"(bk[(jj + 5) & 7]), [b6] "+v"(bk[(jj + 6) & 7])
+                         : SWK_SKEW_IN(pB0, pB1), SWK_SKEW_FOLD(g, 0), SWK_SKEW_FOLD(k, 8),
+                           SWK_SKEW_FOLD(m, 16));
+          else
+            asm volatile(SWK_F16SKEW_L
+                         : SWK_SKEW_OUT(R - 8, "+v", "+v"), [b0] "+v"(bk[0]), [b1] "+v"(bk[1 % NB]),
+                           [b2] "+v"(bk[2 % NB]), [b3] "+v"(bk[3 % NB])
+                         : SWK_SKEW_IN(pB0, pB1), [e1] "s"(e1), SWK_SKEW_FOLD(g, 0),
+                           SWK_SKEW_FOLD(k, 8), SWK_SKEW_FOLD(m, 16));
 #undef SWK_SKEW_FOLD
 #undef SWK_SKEW_OUT
 #undef SWK_SKEW_IN
@@ -823,17 +877,30 @@ __global__ void __launch_bounds__(R >= 64 ? 512 : 1024) score_kernel(const Score
           bal_store((int)blockIdx.x + 1);
         } else {  // this wave's part of tile k is done
         if constexpr (SKEW) {
-          // the last accumulator's move and class 7 of the tile's last column (no later column
-          // runs them), then every accumulator into that frame, 7 + the last column, and out
-          // of it: accumulator a ends the column in frame 2a + 1 + column
+          // the move and class 7 of the tile's last column that the next column's first block
+          // would run, then every accumulator into that frame, 7 + the last column, and out
+          // of it (of 4: accumulator a ends the column in frame 2a + 1 + column)
           // (each two frames on as two adds of e, an SGPR operand: a constant 2e would be
           // loop-invariant and live, a VGPR, across the column loop)
           const f16x2 e1 = as_f16x2(as_u16x2(a.f16_e1));
-          f16x2 bb = fmax2(fmax2(as_f16x2(bk[3]) + e1, as_f16x2(Hl[7])), as_f16x2(Hl[15]));
-          bb = fmax2(fmax2(bb, as_f16x2(Hl[23])), as_f16x2(Hl[31]));
-          f16x2 lo = fmax2((as_f16x2(bk[0]) + e1) + e1, as_f16x2(bk[1]));
-          lo = fmax2((lo + e1) + e1, as_f16x2(bk[2]));
-          bb = fmax2((lo + e1) + e1, bb);
+          f16x2 bb;
+          if constexpr (NB == 8) {
+            // (8: a whole chunk has run, so bk[n] sits in frame 8 (cu + 1) + n, but bk[7], whose
+            // move the next column would run, still in the frame that left, 8 cu + 7; bk[6]
+            // takes class 7 of the last column.  One step of e at a time from the lowest)
+            bb = as_f16x2(bk[7]);
+#pragma unroll
+            for (int i = 0; i < 6; ++i) bb = fmax2(bb + e1, as_f16x2(bk[i]));
+            f16x2 b6 = fmax2(fmax2(as_f16x2(bk[6]), as_f16x2(Hl[7])), as_f16x2(Hl[15]));
+            b6 = fmax2(fmax2(b6, as_f16x2(Hl[23])), as_f16x2(Hl[31]));
+            bb = fmax2(bb + e1, b6);
+          } else {
+            bb = fmax2(fmax2(as_f16x2(bk[3 % NB]) + e1, as_f16x2(Hl[7])), as_f16x2(Hl[15]));
+            bb = fmax2(fmax2(bb, as_f16x2(Hl[23])), as_f16x2(Hl[31]));
+            f16x2 lo = fmax2((as_f16x2(bk[0]) + e1) + e1, as_f16x2(bk[1 % NB]));
+            lo = fmax2((lo + e1) + e1, as_f16x2(bk[2 % NB]));
+            bb = fmax2((lo + e1) + e1, bb);
+          }
           const uint32_t cf = ct[__builtin_amdgcn_readfirstlane(cu * C + ncols + 8)];
           best = as_u16x2(bb - as_f16x2(__builtin_bit_cast(u16x2, cf)));
         }

@@ -479,7 +479,11 @@ sw_status launch(sw_bank* b, const uint8_t* d_res, const uint64_t* d_offs,
                                        gat ? b->glens.p : lens, np,
                                        skew ? b->qpair_skew.p : b->qpair.p, b->nv16, b->S, b->O,
                                        b->E, b->pair_bytes, b->pad, Wl,
-                                       scores, b->pS1, b->pS2, ulen,
+                                       scores, b->pS1, b->pS2,
+                                       // (equal lengths declared through min_len == max_len: the
+                                       // skewed kernels then take a tile's chunk counts from the
+                                       // length, without reducing the lanes' lengths)
+                                       ustride || rbal ? ulen : max_len,
                                        ustride, b->bal_flag.p, b->bal_state.p, ++b->bal_gen, grid,
                                        gat ? nullptr : idx, gat ? nullptr : nidx,
                                        ident, b->bal_plan.p,
