@@ -36,28 +36,17 @@ size_t query_count(const sw_bank* b) { return b->qset.size() > 1 ? b->qset.size(
 // entry per query, the alpha x alpha matrix, then the codes of every query back to back.
 sw_status prepare_align(sw_bank* b) {
   if (b->al_ready) return SW_OK;
-  const size_t nq = query_count(b), ml = b->matrix.size();
+  const size_t nq = query_count(b);
+  const std::vector<uint8_t>* queries = nq > 1 ? b->qset.data() : &b->query;
   size_t ql = 0;
-  for (size_t i = 0; i < nq; ++i) ql += (nq > 1 ? b->qset[i] : b->query).size();
+  for (size_t i = 0; i < nq; ++i) ql += queries[i].size();
   if (ql > 0xFFFFFFFFull)
     return fail(b, SW_ERR_UNSUPPORTED, "alignments: the query set holds more than 2^32 codes");
-  const size_t bytes = nq * sizeof(uint2) + ml + ql;
-  HIPOK(b, hipEventSynchronize(b->ev_ready));  // the staging buffer is free again
-  HIPOK(b, b->stage.reserve(bytes));
-  HIPOK(b, b->al_tab.reserve(bytes));
-  HIPOK(b, hipStreamWaitEvent(b->stream, b->ev_used, 0));
-  uint8_t* codes = b->stage.p + nq * sizeof(uint2) + ml;
-  size_t at = 0;
-  for (size_t i = 0; i < nq; ++i) {
-    const std::vector<uint8_t>& q = nq > 1 ? b->qset[i] : b->query;
-    const uint2 e = make_uint2((uint32_t)at, (uint32_t)q.size());
-    std::memcpy(b->stage.p + i * sizeof(uint2), &e, sizeof(e));
-    if (!q.empty()) std::memcpy(codes + at, q.data(), q.size());
-    at += q.size();
-  }
-  std::memcpy(b->stage.p + nq * sizeof(uint2), b->matrix.data(), ml);
-  HIPOK(b, hipMemcpyAsync(b->al_tab.p, b->stage.p, bytes, hipMemcpyHostToDevice, b->stream));
-  HIPOK(b, hipEventRecord(b->ev_ready, b->stream));
+  const std::vector<uint8_t> t = qtab::build_align(b->matrix, queries, nq);
+  TableUpload up(b);
+  SWOK(up.begin(t.size()));
+  SWOK(up.put(b->al_tab, t));
+  SWOK(up.end());
   b->al_ready = true;
   return SW_OK;
 }

@@ -13,7 +13,8 @@
 // This header also holds what those units share: the buffer types, which free themselves with
 // the bank (DevBuf, UcBuf, PinBuf), the sliced scratch and the staged host batch (SliceScratch,
 // StagedBatch), and the scaffolding of an entry that runs after scoring (root_of, on_root,
-// stream_or, timed_on, scratch_event, slice_plan / slice_reserve, stage_host_batch).
+// stream_or, timed_on, scratch_event, slice_plan / slice_reserve, stage_host_batch), and the
+// upload of query tables (TableUpload; swbank_qtab.h builds them, host-only).
 #ifndef SWBANK_BANK_H
 #define SWBANK_BANK_H
 
@@ -47,6 +48,7 @@
 #include "swbank_align.h"
 #include "swbank_internal.h"
 #include "swbank_pack.h"
+#include "swbank_qtab.h"
 
 extern "C" int swk_has_variant(int R, int RB, int col0, int prof, int gotoh, int f16);
 extern "C" hipError_t swk_launch_wave(int K, int col0, int prof, int gotoh, int f16,
@@ -564,9 +566,9 @@ struct sw_bank {
   DevBuf<uint8_t> fr_hfr;
   DevBuf<int32_t> fr_hsc;
   hipEvent_t ev_frame = nullptr;
-  struct Seg { int W; size_t off, off16; };  // rows = W*R (last may be shorter); word offsets
-                                              // in qtab and qtab16
+  using Seg = qtab::Seg;  // rows = W*R (last may be shorter); word offsets in qtab and qtab16
   std::vector<Seg> segs;
+  qtab::Plan plan;  // prepare()'s analysis: what the set's and the int32 tables are built from
   DevBuf<uint2> edge[2];  // bottom rows handed from segment to segment
   // wave kernel (few targets, query <= 1024 rows): lane l owns rows [lK, lK+K)
   int wK = 0;              // rows per lane: 4, 8 or 16 (16 with several segments)
@@ -727,13 +729,6 @@ struct DevGuard {
   DevGuard& operator=(const DevGuard&) = delete;
 };
 
-// Scores in the f16 kernels are f16 multiples of 2^-11 (x as x/2048, swbank_kcommon.h), so
-// the packed add's [0, 1] clamp is max(0, x); -2048 (padding rows / letters) is 0xBC00.
-inline uint16_t f16_score_bits(int v) {
-  return __builtin_bit_cast(uint16_t, (_Float16)((float)v * (1.0f / 2048.0f)));
-}
-
-
 // Sets the bank's error text (sw_last_error) and returns st.
 sw_status fail(sw_bank* b, sw_status st, const char* fmt, ...);
 
@@ -743,6 +738,12 @@ sw_status fail(sw_bank* b, sw_status st, const char* fmt, ...);
     if (e_ != hipSuccess)                                                                 \
       return fail((bank), SW_ERR_HIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_),    \
                   __FILE__, __LINE__);                                                    \
+  } while (0)
+
+#define SWOK(expr)                       \
+  do {                                   \
+    const sw_status s_ = (expr);         \
+    if (s_ != SW_OK) return s_;          \
   } while (0)
 
 struct Timed {  // one bracketed launch group (sw_bank_set_timing)
@@ -827,6 +828,41 @@ inline sw_status scratch_event(sw_bank* b, hipEvent_t& ev, hipStream_t hs) {
     HIPOK(b, hipStreamWaitEvent(hs, ev, 0));
   return SW_OK;
 }
+
+// One upload of query tables on the bank stream, the protocol sw_bank states at ev_ready /
+// ev_used (both exist: prepare() creates them).  begin(bytes): on the bank's device, the previous
+// upload has left the staging buffer, the buffer holds `bytes`, and the bank stream waits for the
+// launches that may still read the tables.  put(dst, src): reserves dst, stages src at the next
+// offset and queues its copy (an empty src: nothing but the reserve).  end(): records ev_ready.
+class TableUpload {
+ public:
+  explicit TableUpload(sw_bank* b) : b(b) {}
+  sw_status begin(size_t bytes) {
+    HIPOK(b, hipSetDevice(b->device));
+    HIPOK(b, hipEventSynchronize(b->ev_ready));
+    HIPOK(b, b->stage.reserve(bytes));
+    HIPOK(b, hipStreamWaitEvent(b->stream, b->ev_used, 0));
+    return SW_OK;
+  }
+  template <class T, class U>
+  sw_status put(DevBuf<T>& dst, const std::vector<U>& src) {
+    const size_t bytes = src.size() * sizeof(U);
+    HIPOK(b, dst.reserve((bytes + sizeof(T) - 1) / sizeof(T)));
+    if (!bytes) return SW_OK;
+    std::memcpy(b->stage.p + at, src.data(), bytes);
+    HIPOK(b, hipMemcpyAsync(dst.p, b->stage.p + at, bytes, hipMemcpyHostToDevice, b->stream));
+    at += bytes;
+    return SW_OK;
+  }
+  sw_status end() {
+    HIPOK(b, hipEventRecord(b->ev_ready, b->stream));
+    return SW_OK;
+  }
+
+ private:
+  sw_bank* b;
+  size_t at = 0;
+};
 
 // The slices of a call over n targets of at most max_len codes against nq queries: `codes`
 // when the slice holds codes of its own (at stride round16(max_len) + 16, with an offset per

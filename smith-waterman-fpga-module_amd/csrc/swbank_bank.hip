@@ -512,43 +512,18 @@ extern "C" size_t sw_query_count(const sw_bank* b) {
   return !b || !b->have_query ? 0 : b->qset.size() > 1 ? b->qset.size() : 1;
 }
 
-// Letter-pair table layout for NR rows: slot (a, b) at 16 + a*pS1 + b*pS2 (bytes), pS2/16 = 1 and
-// pS1/16 = 4 (mod 16) so the 16 A/C/G/T slots sit on 16 different 4-bank LDS groups.
-static void pair_strides(uint32_t NR, uint32_t& pS1, uint32_t& pS2) {
-  const uint32_t B = 4 * NR;
-  pS2 = (B + 15) / 16 * 16;
-  while ((pS2 / 16) % 16 != 1) pS2 += 16;
-  pS1 = (4 * pS2 + B + 15) / 16 * 16;
-  while ((pS1 / 16) % 16 != 4) pS1 += 16;
-}
-
-// The letter-pair table of query rows [r0, r0 + NR) (the PAIR tile kernel, DNA merged f16):
-// slot (a, b) holds word k = {s(q_{r0+k+1}, a), s(q_{r0+k+1}, b)} (f16 halves; rows past the
-// query -2048) and the row-r0 word 4 bytes before it.
-// add / pad: the skewed rows' table holds s + add (add = 2e) and pad + add in rows past the query
-// (the unskewed kernel's: s, -2048); add0: what the first row of every 8-row block holds on top
-// (the skewed rows' -8e: the row above it sits 7 frames on), pad rows too.
-static std::vector<uint32_t> pair_table(const uint8_t* q, int qlen, int r0, uint32_t NR,
-                                        const int8_t* m, int A, uint32_t pS1, uint32_t pS2,
-                                        int add = 0, int pad = -2048, int add0 = 0) {
-  const uint32_t bytes = 16 + 4 * pS1 + 4 * pS2 + 4 * NR;
-  const uint32_t padw = (uint32_t)f16_score_bits(pad + add) * 0x10001u;
-  std::vector<uint32_t> t(bytes / 4, padw);
-  auto word = [&](int r, int x, int y) -> uint32_t {  // row r of the segment, letters x, y
-    const int ad = add + (r % 8 == 0 ? add0 : 0);
-    if (r0 + r >= qlen) return (uint32_t)f16_score_bits(pad + ad) * 0x10001u;
-    const int c = q[r0 + r];
-    return (uint32_t)f16_score_bits(m[c * A + x] + ad) |
-           (uint32_t)f16_score_bits(m[c * A + y] + ad) << 16;
-  };
-  for (int x = 0; x < A; ++x)
-    for (int y = 0; y < A; ++y) {
-      const uint32_t base = (16 + x * pS1 + y * pS2) / 4;
-      for (uint32_t k = 0; k + 1 < NR; ++k) t[base + k] = word((int)k + 1, x, y);
-    }
-  for (int x = 0; x < A; ++x)  // row-0 words last: they may reuse word NR-1 of a slot
-    for (int y = 0; y < A; ++y) t[(16 + x * pS1 + y * pS2) / 4 - 1] = word(0, x, y);
-  return t;
+// ---- the query tables: built on the host by swbank_qtab.h, uploaded by TableUpload -------------
+// The tuning knobs of the table construction (qtab::Options): the environment is read here only.
+static qtab::Options table_options() {
+  qtab::Options o;
+  o.profile = env_int("SWBANK_PROFILE", 0);
+  o.R = env_int("SWBANK_R", 0);
+  o.RB = env_int("SWBANK_RB", 0);
+  o.seg = env_int("SWBANK_SEG", 0);
+  o.f16 = env_int("SWBANK_F16", 1);
+  o.mq_pair = env_int("SWBANK_MQ_PAIR", 1);
+  o.mq_pair_rows = env_int("SWBANK_MQ_PAIR_ROWS", 128);
+  return o;
 }
 
 // Build the resident query state (the ScoringModule's query + penalty registers,
@@ -558,255 +533,17 @@ sw_status prepare(sw_bank* b) {
   if (!b->have_pen || !b->have_query)
     return fail(b, SW_ERR_STATE, "load penalties (ld_penalties) and a query (ld_sequence) first");
   if (!b->dirty) return SW_OK;
-  const int A = b->alpha;
+  // analyse
   const int8_t* m = b->matrix.data();
-  int smax = -128, smin = 127;
-  for (int i = 0; i < A * A; ++i) {
-    smax = std::max<int>(smax, m[i]);
-    smin = std::min<int>(smin, m[i]);
-  }
-  const int S = std::max(0, smax);
-  if (S - smin > 254)
-    return fail(b, SW_ERR_RANGE, "substitution range [%d, %d] exceeds 254", smin, smax);
-  const int o = -b->gap_open, e = -b->gap_extend;
-  const bool gotoh = b->cfg.gap_model == SW_GAP_GOTOH;
-  if (gotoh && o + e + S > 65535) return fail(b, SW_ERR_RANGE, "gap penalties too large");
-
-  // LUT mode needs a DNA matrix whose N column (codes 4..7 share one word) is uniform and <= 0
-  bool lut = A == SW_DNA_ALPHA;
-  const int sN = m[4];
-  for (int i = 0; lut && i < A; ++i) lut = m[i * A + 4] == sN;
-  lut = lut && sN <= 0;
-  // The f16 LUT holds one byte per entry (the f16 high byte): only scores whose f16 low byte
-  // is 0 (|s| <= 8, or coarser even values) qualify.  Other DNA matrices run in profile mode
-  // (2-byte f16 entries) when f16 applies at all: faster than the u16 LUT kernel.
-  bool lut_f16 = true;
-  for (int i = 0; i < A * A; ++i) {
-    const uint16_t bits = f16_score_bits(m[i]);
-    lut_f16 = lut_f16 && (bits & 0xFFu) == 0;
-  }
-  const bool f16_range = -(o + 2 * e + (std::max(0, smax) - smin)) >= -2048;
-  const int prof =
-      (env_int("SWBANK_PROFILE", 0) || !lut || (!lut_f16 && f16_range)) ? 1 : 0;
-
-  const int qlen = (int)b->query.size();
-  // the HDL column-0 rule differs from the plain recurrence only if a match pays for a gap
-  const int col0 = (!gotoh && smax > o + e) ? 1 : 0;
-  // Rows per wave: 32 for the DNA LUT kernels (merged and Gotoh: the Gotoh f16 column with
-  // the letter-pair table runs 8.3-8.6 TCUPS at R = 32 against 7.8-8.2 at R = 16, and a
-  // 512-row query fits one workgroup); 16 for tiny queries and for the profile / column-0
-  // variants, whose 32-row columns do not fit 128 VGPRs (the occupancy-4 budget) without
-  // spilling.  Queries longer than one workgroup (16 waves) run
-  // as segments of SWBANK_SEG rows (default: a full 16-wave workgroup, 16·R rows), each
-  // segment's bottom row handed to the next through HBM.  SWBANK_R / SWBANK_RB / SWBANK_SEG
-  // override (tuning only).
-  // u16 Gotoh keeps R = 16 when no f16 pass can run (its 32-row column spills past 128 VGPRs);
-  // u16 passes that follow an f16 pass (optimistic re-scores) are rare and use the f16 layout
-  const bool u16_only = gotoh && (!f16_range || env_int("SWBANK_F16", 1) == 0);
-  int R = (qlen <= 16 || prof || col0 || u16_only) ? 16 : 32, RB = 4;
-  R = env_int("SWBANK_R", R);
-  RB = env_int("SWBANK_RB", RB);
-  const int max_rows = (R >= 64 ? 8 : 16) * R;
-  int seg_rows = qlen > max_rows ? env_int("SWBANK_SEG", max_rows)
-                                 : std::max(qlen, 1);
-  if (seg_rows % R != 0 && seg_rows < qlen)
-    return fail(b, SW_ERR_ARG, "segment rows %d not a multiple of R=%d", seg_rows, R);
-  if (!swk_has_variant(R, RB, col0, prof, gotoh ? 1 : 0, 0))
-    return fail(b, SW_ERR_UNSUPPORTED, "no kernel variant R=%d RB=%d col0=%d prof=%d gotoh=%d", R,
-                RB, col0, prof, (int)gotoh);
-  const int Wseg = std::max(1, (seg_rows + R - 1) / R);
-  if (Wseg * 64 > (R >= 64 ? 512 : 1024))
-    return fail(b, SW_ERR_UNSUPPORTED, "segment of %d rows too tall for one workgroup", seg_rows);
-
-  // per segment: LUT words (W*R) or a query profile ((A+1) x PS bytes), concatenated
-  std::vector<uint32_t> tab;
-  std::vector<sw_bank::Seg> segs;
-  // profile row stride: a multiple of 16 B that is 16 mod 256, so the 16-B reads of lanes
-  // holding different letters fall in different LDS banks (a stride of 0 mod 256 puts every
-  // letter row on the same 4 banks)
-  uint32_t PS = prof ? (uint32_t)((Wseg * R + 15) / 16 * 16) : 0;
-  if (prof) PS += (16u + 256u - PS % 256u) % 256u;
-  const uint32_t pad = prof ? (uint32_t)A : 4u;  // profile letter A = padding row (all 0xFF)
-  const uint32_t nv = prof ? 0u : (uint32_t)(uint8_t)(S - sN) * 0x01010101u;
-  for (int r0 = 0; r0 < std::max(qlen, 1); r0 += seg_rows) {
-    const int rows = std::min(seg_rows, std::max(qlen, 1) - r0);
-    const int W = std::max(1, (rows + R - 1) / R);
-    segs.push_back({W, tab.size(), 0});
-    if (!prof) {
-      const size_t base = tab.size();
-      tab.resize(base + (size_t)W * R, 0xFFFFFFFFu);
-      for (int i = 0; i < rows && r0 + i < qlen; ++i) {
-        uint32_t w = 0;
-        for (int c = 0; c < 4; ++c)
-          w |= (uint32_t)(uint8_t)(S - m[b->query[r0 + i] * A + c]) << (8 * c);
-        tab[base + i] = w;
-      }
-    } else {
-      std::vector<uint8_t> qp((size_t)(A + 1) * PS, 0xFF);
-      for (int c = 0; c < A; ++c)
-        for (int i = 0; i < rows && r0 + i < qlen; ++i)
-          qp[(size_t)c * PS + i] = (uint8_t)(S - m[b->query[r0 + i] * A + c]);
-      const size_t base = tab.size();
-      tab.resize(base + qp.size() / 4);
-      std::memcpy(tab.data() + base, qp.data(), qp.size());
-    }
-  }
-  // f16 variant of the LUT: each substitution score must be an f16 whose low byte is 0
-  // (|s| <= 8 or a coarser even value), so the byte perm yields the exact f16 bits
-  auto f16_hi = [](int v, uint8_t* out) {
-    const uint16_t bits = f16_score_bits(v);
-    *out = (uint8_t)(bits >> 8);
-    return (bits & 0xFFu) == 0 &&
-           (int)((float)__builtin_bit_cast(_Float16, bits) * 2048.0f) == v;
-  };
-  // LUT mode: one byte per entry (the f16 high byte); profile mode: two bytes (any |s| <= 127
-  // is an exact f16), row stride PS16 = 2 x rows, 16 mod 256 like PS
-  bool f16 = swk_has_variant(R, RB, col0, prof, gotoh ? 1 : 0, 1) != 0;
-  std::vector<uint32_t> tab16;
-  uint8_t hN = 0;
-  uint32_t PS16 = 0;
-  if (!prof) {
-    f16 = f16 && f16_hi(sN, &hN);
-    for (int i = 0; f16 && i < A * A; ++i) {
-      uint8_t h;
-      f16 = f16_hi(m[i], &h);
-    }
-  }
-  if (f16 && !prof) {
-    tab16.assign(tab.size(), 0xBCBCBCBCu);  // padding rows: -2048
-    for (sw_bank::Seg& sg : segs) {
-      const int r0 = (int)(&sg - segs.data()) * seg_rows;
-      sg.off16 = sg.off;
-      for (int i = 0; i < sg.W * R && r0 + i < qlen && i < seg_rows; ++i) {
-        uint32_t w = 0;
-        for (int c = 0; c < 4; ++c) {
-          uint8_t h;
-          f16_hi(m[b->query[r0 + i] * A + c], &h);
-          w |= (uint32_t)h << (8 * c);
-        }
-        tab16[sg.off + i] = w;
-      }
-    }
-  } else if (f16) {
-    PS16 = (uint32_t)((2 * Wseg * R + 15) / 16 * 16);
-    PS16 += (16u + 256u - PS16 % 256u) % 256u;
-    const uint16_t padv = 0xBC00u;  // -2048: padding letter and rows past the query
-    for (sw_bank::Seg& sg : segs) {
-      const int r0 = (int)(&sg - segs.data()) * seg_rows;
-      std::vector<uint16_t> qp((size_t)(A + 1) * PS16 / 2, padv);
-      for (int c = 0; c < A; ++c)
-        for (int i = 0; i < sg.W * R && r0 + i < qlen && i < seg_rows; ++i)
-          qp[(size_t)c * PS16 / 2 + i] =
-              f16_score_bits(m[b->query[r0 + i] * A + c]);
-      sg.off16 = tab16.size();
-      tab16.resize(sg.off16 + qp.size() / 2);
-      std::memcpy(tab16.data() + sg.off16, qp.data(), qp.size() * 2);
-    }
-  }
-  // Letter-pair table for the PAIR tile kernel (SWBANK_PAIR=0 at launch time disables it):
-  // DNA merged gaps,
-  // the f16 LUT kernel's R = 32, one segment of at most 4 waves (the table's 25 slots then fit
-  // beside the ring at 4 workgroups per CU).  Slot (a, b) at 16 + a*S1 + b*S2 holds word k =
-  // {s(q_{k+1}, a), s(q_{k+1}, b)} (f16 halves; rows past the query -2048) and the row-0 word
-  // 4 bytes before it.  S2/16 = 1 and S1/16 = 4 (mod 16) put the 16 A/C/G/T slots on 16
-  // different 4-bank LDS groups.
-  // DNA Gotoh (R = 16): one table per query segment, each of the tallest segment's rows (the
-  // Gotoh column is 7.5 VALU per 2 cells from the table against 8.5 with the row LUT).
-  std::vector<uint32_t> tpair;
-  uint32_t pS1 = 0, pS2 = 0, pair_words = 0;
-  if (f16 && !prof && !col0 && A == SW_DNA_ALPHA &&
-      (gotoh ? R == 16 || R == 32 : R == 32 && segs.size() == 1 && segs[0].W <= 4)) {
-    const uint32_t NR = (uint32_t)segs[0].W * R;
-    pair_strides(NR, pS1, pS2);
-    for (size_t sg = 0; sg < segs.size(); ++sg) {
-      const std::vector<uint32_t> t =
-          pair_table(b->query.data(), qlen, (int)sg * seg_rows, NR, m, A, pS1, pS2);
-      pair_words = (uint32_t)t.size();
-      tpair.insert(tpair.end(), t.begin(), t.end());
-    }
-  }
-  // The skewed rows of the merged pair kernel: the same table with s + 2e (the
-  // first row of every 8-row block s + 2e - 8e), rows past the query with a score no H can lift
-  // above 0 (H <= max(s) x rows; the same score in every row, so that skew_neg, and with it
-  // launch()'s choice, is what it was before the frames restarted every 8 rows), and the floors
-  // c_k = e (k - 1) of the frames k = (row mod 8) + column, word k + 2.  launch() takes them when
-  // a batch's values fit f16 with the offsets.
-  std::vector<uint32_t> tskew, tfloor;
-  int skew_neg = 0;
-  if (!tpair.empty() && !gotoh && 2 * e <= 2048) {
-    const int spad = -std::min(2048 - 2 * e, S * std::max(qlen, 1));
-    tskew = pair_table(b->query.data(), qlen, 0, (uint32_t)segs[0].W * R, m, A, pS1, pS2, 2 * e,
-                       spad, -8 * e);
-    tfloor.resize(2048 + 32);
-    for (size_t k = 0; k < tfloor.size(); ++k)
-      tfloor[k] = (uint32_t)f16_score_bits(std::min(2048, e * ((int)k - 3))) * 0x10001u;
-    // the most negative value that has to be exact: A - o of a block's first row in frame 0,
-    // A = c_6 + min(s, pad) + 2e - 8e.  (The T~ of the row above, shifted into that frame, can
-    // lie e lower; it is far below every floor and only ever enters a max)
-    skew_neg = 5 * e + std::min(smin, spad) + 2 * e - 8 * e - o;
-  }
-  // wave-kernel layout of the same query: rows padded to 64K; queries past 1024 rows run as
-  // 1024-row segments (K = 16), one table per segment, concatenated
-  const auto wave_tables = [&](int wrows, int nsegs, std::vector<uint32_t>& wt,
-                               std::vector<uint32_t>& wt16) {
-    for (int sg = 0; sg < nsegs; ++sg) {
-      const int r0 = sg * wrows, nr = std::min(wrows, std::max(0, qlen - r0));
-      if (!prof) {
-        const size_t base = wt.size();
-        wt.resize(base + wrows, 0xFFFFFFFFu);
-        for (int i = 0; i < nr; ++i) {
-          uint32_t w = 0;
-          for (int c = 0; c < 4; ++c)
-            w |= (uint32_t)(uint8_t)(S - m[b->query[r0 + i] * A + c]) << (8 * c);
-          wt[base + i] = w;
-        }
-        if (f16) {
-          const size_t b16 = wt16.size();
-          wt16.resize(b16 + wrows, 0xBCBCBCBCu);  // rows past the query: -2048
-          for (int i = 0; i < nr; ++i) {
-            uint32_t w = 0;
-            for (int c = 0; c < 4; ++c) {
-              uint8_t h;
-              f16_hi(m[b->query[r0 + i] * A + c], &h);
-              w |= (uint32_t)h << (8 * c);
-            }
-            wt16[b16 + i] = w;
-          }
-        }
-      } else {
-        std::vector<uint8_t> qp((size_t)(A + 1) * wrows, 0xFF);
-        for (int c = 0; c < A; ++c)
-          for (int i = 0; i < nr; ++i)
-            qp[(size_t)c * wrows + i] = (uint8_t)(S - m[b->query[r0 + i] * A + c]);
-        const size_t base = wt.size();
-        wt.resize(base + qp.size() / 4);
-        std::memcpy(wt.data() + base, qp.data(), qp.size());
-        if (f16) {
-          std::vector<uint16_t> q16((size_t)(A + 1) * wrows, 0xBC00u);
-          for (int c = 0; c < A; ++c)
-            for (int i = 0; i < nr; ++i)
-              q16[(size_t)c * wrows + i] = f16_score_bits(m[b->query[r0 + i] * A + c]);
-          const size_t b16 = wt16.size();
-          wt16.resize(b16 + q16.size() / 2);
-          std::memcpy(wt16.data() + b16, q16.data(), q16.size() * 2);
-        }
-      }
-    }
-  };
-  std::vector<uint32_t> wt, wt16;
-  const int wK = qlen <= 256 ? 4 : qlen <= 512 ? 8 : 16;
-  const int wrows = 64 * wK;
-  const int wsegs = std::max(1, (qlen + wrows - 1) / wrows);
-  const uint32_t wPS = prof ? (uint32_t)wrows : 0, wPS16 = prof ? (uint32_t)wrows * 2 : 0;
-  wave_tables(wrows, wsegs, wt, wt16);
-  // split tail of the wave kernel (one segment, K >= 8): the query as P = 2, 4 and 8 segments
-  // of K/P rows per lane, tables concatenated like the segments above
-  std::vector<uint32_t> st[3], st16[3];
-  int sK[3] = {0, 0, 0};
-  for (int i = 0; i < 3; ++i) {
-    sK[i] = (wsegs == 1 && wK >= 8) ? wK / (2 << i) : 0;
-    if (sK[i]) wave_tables(64 * sK[i], 2 << i, st[i], st16[i]);
-  }
+  const qtab::Plan p = qtab::analyse(
+      m, b->alpha, b->gotoh(), b->gap_open, b->gap_extend, (int)b->query.size(), table_options(),
+      [](const qtab::Plan& q, int f16) {
+        return swk_has_variant(q.R, q.RB, q.col0, q.prof, q.gotoh ? 1 : 0, f16) != 0;
+      });
+  if (p.status != SW_OK) return fail(b, p.status, "%s", p.msg);
+  // build
+  const qtab::QueryTables t = qtab::build_query(p, m, b->query.data());
+  // upload
   HIPOK(b, hipSetDevice(b->device));
   if (!b->ev_ready) {
     HIPOK(b, hipEventCreateWithFlags(&b->ev_ready, hipEventDisableTiming));
@@ -814,72 +551,55 @@ sw_status prepare(sw_bank* b) {
     HIPOK(b, hipEventRecord(b->ev_ready, b->stream));
     HIPOK(b, hipEventRecord(b->ev_used, b->stream));
   }
-  // the previous upload must have left the staging buffer before it is refilled
-  HIPOK(b, hipEventSynchronize(b->ev_ready));
-  const size_t nbytes =
-      (wt16.size() + wt.size() + st16[0].size() + st[0].size() + st16[1].size() +
-       st[1].size() + st16[2].size() + st[2].size() + tab.size() + tab16.size() + tpair.size() +
-       tskew.size() + tfloor.size()) *
-      4;
-  HIPOK(b, b->stage.reserve(nbytes));
-  // earlier launches (any stream) must be done reading the tables this upload overwrites
-  HIPOK(b, hipStreamWaitEvent(b->stream, b->ev_used, 0));
-  size_t at = 0;
-  auto upload = [&](DevBuf<uint32_t>& dst, const std::vector<uint32_t>& src) -> hipError_t {
-    hipError_t e = dst.reserve(src.size());
-    if (e != hipSuccess || src.empty()) return e;
-    std::memcpy(b->stage.p + at, src.data(), src.size() * 4);
-    e = hipMemcpyAsync(dst.p, b->stage.p + at, src.size() * 4, hipMemcpyHostToDevice, b->stream);
-    at += src.size() * 4;
-    return e;
-  };
-  if (!wt16.empty()) HIPOK(b, upload(b->wtab16, wt16));
-  HIPOK(b, upload(b->wtab, wt));
-  b->wPS16 = wPS16;
-  b->wK = wK;
-  b->wPS = wPS;
-  b->wsegs = wsegs;
-  b->wseg_words = wt.size() / wsegs;
-  b->wseg_words16 = wt16.empty() ? 0 : wt16.size() / wsegs;
+  const std::pair<DevBuf<uint32_t>*, const std::vector<uint32_t>*> tables[] = {
+      {&b->wtab16, &t.wt16},       {&b->wtab, &t.wt},       {&b->stab16[0], &t.st16[0]},
+      {&b->stab[0], &t.st[0]},     {&b->stab16[1], &t.st16[1]}, {&b->stab[1], &t.st[1]},
+      {&b->stab16[2], &t.st16[2]}, {&b->stab[2], &t.st[2]}, {&b->qtab, &t.tab},
+      {&b->qtab16, &t.tab16},      {&b->qpair, &t.tpair},   {&b->qpair_skew, &t.tskew},
+      {&b->skew_ctab, &t.tfloor}};
+  size_t words = 0;
+  for (const auto& u : tables) words += u.second->size();
+  TableUpload up(b);
+  SWOK(up.begin(words * 4));
+  for (const auto& u : tables) SWOK(up.put(*u.first, *u.second));
+  SWOK(up.end());
+  // store
+  b->plan = p;
+  b->segs = t.segs;
+  b->R = p.R;
+  b->RB = p.RB;
+  b->W = t.segs[0].W;
+  b->col0 = p.col0;
+  b->prof = p.prof;
+  b->S = (uint32_t)p.S;
+  b->O = (uint32_t)p.o;
+  b->E = (uint32_t)p.e;
+  b->smax = p.smax;
+  b->nv = p.nv;
+  b->PS = p.PS;
+  b->pad = p.pad;
+  b->f16 = p.f16;
+  b->nv16 = p.nv16;
+  b->PS16 = p.PS16;
+  b->f16_neg = p.f16_neg;
+  b->pair_bytes = t.pair_words * 4;  // one segment's table
+  b->pS1 = t.pS1;
+  b->pS2 = t.pS2;
+  b->skew_entries = (uint32_t)t.tfloor.size();
+  b->skew_neg = t.skew_neg;
+  b->wK = p.wK;
+  b->wsegs = p.wsegs;
+  b->wPS = p.prof ? (uint32_t)(64 * p.wK) : 0;
+  b->wPS16 = p.prof ? (uint32_t)(128 * p.wK) : 0;
+  b->wseg_words = t.wt.size() / p.wsegs;
+  b->wseg_words16 = t.wt16.size() / p.wsegs;
   for (int i = 0; i < 3; ++i) {
-    if (!st16[i].empty()) HIPOK(b, upload(b->stab16[i], st16[i]));
-    HIPOK(b, upload(b->stab[i], st[i]));
-    b->sK[i] = sK[i];
-    b->sseg_words[i] = st[i].size() / (2 << i);
-    b->sseg_words16[i] = st16[i].size() / (2 << i);
-    b->sPS[i] = prof ? (uint32_t)(64 * sK[i]) : 0;
-    b->sPS16[i] = prof ? (uint32_t)(128 * sK[i]) : 0;
+    b->sK[i] = p.sK[i];
+    b->sseg_words[i] = t.st[i].size() / (2 << i);
+    b->sseg_words16[i] = t.st16[i].size() / (2 << i);
+    b->sPS[i] = p.prof ? (uint32_t)(64 * p.sK[i]) : 0;
+    b->sPS16[i] = p.prof ? (uint32_t)(128 * p.sK[i]) : 0;
   }
-  HIPOK(b, upload(b->qtab, tab));
-  if (f16) HIPOK(b, upload(b->qtab16, tab16));
-  if (!tpair.empty()) HIPOK(b, upload(b->qpair, tpair));
-  if (!tskew.empty()) {
-    HIPOK(b, upload(b->qpair_skew, tskew));
-    HIPOK(b, upload(b->skew_ctab, tfloor));
-  }
-  b->skew_entries = tskew.empty() ? 0u : (uint32_t)tfloor.size();
-  b->skew_neg = skew_neg;
-  b->pair_bytes = pair_words * 4;  // one segment's table
-  b->pS1 = pS1;
-  b->pS2 = pS2;
-  HIPOK(b, hipEventRecord(b->ev_ready, b->stream));
-  b->f16 = f16;
-  b->nv16 = (uint32_t)hN * 0x01010101u;
-  b->PS16 = PS16;
-  b->f16_neg = -(o + 2 * e + (S - smin));
-  b->R = R;
-  b->RB = RB;
-  b->W = segs[0].W;
-  b->segs = segs;
-  b->S = (uint32_t)S;
-  b->O = (uint32_t)o;
-  b->E = (uint32_t)e;
-  b->nv = nv;
-  b->PS = PS;
-  b->pad = pad;
-  b->prof = prof;
-  b->smax = smax;
-  b->col0 = col0;
   b->i32_ready = false;
   b->al_ready = false;
   b->mq_ready = false;
@@ -888,115 +608,41 @@ sw_status prepare(sw_bank* b) {
 }
 
 // Row-LUT tables of every query of a set in the segment layout of the longest one (prepare()
-// ran on it): query i's words at i * mq_words, rows past its end padding (u16 0xFF: S - 255,
-// f16 0xBC: -2048, as in prepare()).  LUT mode only (DNA matrices without the column-0 rule).
+// ran on it): query i's words at i * mq_words, and the set's letter-pair tables (qtab::SetTables).
 sw_status prepare_multi(sw_bank* b) {
   if (b->mq_ready) return SW_OK;
-  const int A = b->alpha;
-  const int8_t* m = b->matrix.data();
-  const int R = b->R, S = (int)b->S;
-  const size_t words = b->segs.back().off + (size_t)b->segs.back().W * R;
-  const int seg_rows = b->segs[0].W * R;
-  const size_t nq = b->qset.size();
-  std::vector<uint32_t> t16, t8(nq * words, 0xFFFFFFFFu);
-  if (b->f16) t16.assign(nq * words, 0xBCBCBCBCu);
-  for (size_t i = 0; i < nq; ++i) {
-    const std::vector<uint8_t>& qi = b->qset[i];
-    for (size_t sg = 0; sg < b->segs.size(); ++sg) {
-      const size_t base = i * words + b->segs[sg].off;
-      const int r0 = (int)sg * seg_rows;
-      for (int j = 0; j < b->segs[sg].W * R && r0 + j < (int)qi.size(); ++j) {
-        uint32_t w = 0, h = 0;
-        for (int c = 0; c < 4; ++c) {
-          const int v = m[qi[r0 + j] * A + c];
-          w |= (uint32_t)(uint8_t)(S - v) << (8 * c);
-          h |= (uint32_t)(f16_score_bits(v) >> 8) << (8 * c);
-        }
-        t8[base + j] = w;
-        if (b->f16) t16[base + j] = h;
-      }
-    }
-  }
-  // letter-pair tables (DNA merged f16 without the column-0 rule), one per (segment, query):
-  // 128-row segments (4 waves of 32 rows, 4-column chunks, 4 workgroups per CU whose wave
-  // priorities rotate: a 1-kbp query is 8 segments, 7 bottom-row hand-offs through HBM; +11 %
-  // against 512-row segments, one workgroup per CU) unless SWBANK_MQ_PAIR_ROWS=256
-  // (8 waves, 2 workgroups per CU) or 512 (16 waves)
-  std::vector<uint32_t> tp;
-  b->mq_pair_segs = 0;
-  if (b->f16 && !b->prof && !b->gotoh() && !b->col0 && A == SW_DNA_ALPHA &&
-      env_int("SWBANK_MQ_PAIR", 1) != 0) {
-    const int want = env_int("SWBANK_MQ_PAIR_ROWS", 128);
-    const uint32_t NR = want == 128 ? 128 : want == 256 ? 256 : 512;
-    b->mq_pair_rows = (int)NR;
-    pair_strides(NR, b->mq_pS1, b->mq_pS2);
-    const int qmax = (int)b->query.size();
-    b->mq_pair_segs = std::max(1, (qmax + (int)NR - 1) / (int)NR);
-    for (int sg = 0; sg < b->mq_pair_segs; ++sg)
-      for (size_t i = 0; i < nq; ++i) {
-        const std::vector<uint32_t> t = pair_table(b->qset[i].data(), (int)b->qset[i].size(),
-                                                   sg * (int)NR, NR, m, A, b->mq_pS1, b->mq_pS2);
-        b->mq_pair_words = t.size();
-        tp.insert(tp.end(), t.begin(), t.end());
-      }
-  }
-  HIPOK(b, hipSetDevice(b->device));
-  HIPOK(b, hipEventSynchronize(b->ev_ready));  // the staging buffer is free again
-  HIPOK(b, b->stage.reserve((t8.size() + t16.size() + tp.size()) * 4));
-  HIPOK(b, b->mqtab.reserve(t8.size()));
-  if (!t16.empty()) HIPOK(b, b->mqtab16.reserve(t16.size()));
-  HIPOK(b, hipStreamWaitEvent(b->stream, b->ev_used, 0));
-  std::memcpy(b->stage.p, t8.data(), t8.size() * 4);
-  HIPOK(b, hipMemcpyAsync(b->mqtab.p, b->stage.p, t8.size() * 4, hipMemcpyHostToDevice,
-                          b->stream));
-  if (!t16.empty()) {
-    std::memcpy(b->stage.p + t8.size() * 4, t16.data(), t16.size() * 4);
-    HIPOK(b, hipMemcpyAsync(b->mqtab16.p, b->stage.p + t8.size() * 4, t16.size() * 4,
-                            hipMemcpyHostToDevice, b->stream));
-  }
-  if (!tp.empty()) {
-    const size_t at = (t8.size() + t16.size()) * 4;
-    HIPOK(b, b->mqpair.reserve(tp.size()));
-    std::memcpy(b->stage.p + at, tp.data(), tp.size() * 4);
-    HIPOK(b, hipMemcpyAsync(b->mqpair.p, b->stage.p + at, tp.size() * 4, hipMemcpyHostToDevice,
-                            b->stream));
-  }
-  HIPOK(b, hipEventRecord(b->ev_ready, b->stream));
-  b->mq_words = words;
+  const qtab::SetTables t =
+      qtab::build_set(b->plan, b->segs, b->matrix.data(), b->qset, table_options());
+  TableUpload up(b);
+  SWOK(up.begin((t.t8.size() + t.t16.size() + t.tp.size()) * 4));
+  SWOK(up.put(b->mqtab, t.t8));
+  SWOK(up.put(b->mqtab16, t.t16));
+  SWOK(up.put(b->mqpair, t.tp));
+  SWOK(up.end());
+  b->mq_words = t.words;
+  b->mq_pair_words = t.pair_words;
+  b->mq_pair_segs = t.pair_segs;
+  b->mq_pair_rows = t.pair_rows;
+  b->mq_pS1 = t.pS1;
+  b->mq_pS2 = t.pS2;
   b->mq_ready = true;
   return SW_OK;
 }
 
 // int32 re-score state, built on first use per (penalties, query): the per-strip profile of
-// swk_launch_i32 ([strip][letter 0..pad][lane] 4 x int16: rows 4l..4l+3 of a 256-row strip;
-// letter = min(code, pad) as in the 16-bit kernels, the padding letter scoring S - 255 like
-// their padding row), uploaded on the bank stream like the other query tables.
+// swk_launch_i32 (qtab::build_i32), uploaded on the bank stream like the other query tables.
 sw_status prepare_i32(sw_bank* b) {
   if (b->i32_ready) return SW_OK;
-  const int A = b->alpha;
-  const int8_t* m = b->matrix.data();
-  const uint32_t qlen = (uint32_t)b->query.size();
-  const uint32_t strips = std::max(1u, (qlen + 255) / 256), pad = b->pad;
-  if (pad + 1 > 25) return fail(b, SW_ERR_UNSUPPORTED, "int32 kernel: alphabet %d too large", A);
-  std::vector<int16_t> h((size_t)strips * (pad + 1) * 64 * 4, 0);
-  for (uint32_t s = 0; s < strips; ++s)
-    for (uint32_t c = 0; c <= pad; ++c)
-      for (uint32_t l = 0; l < 64; ++l)
-        for (uint32_t k = 0; k < 4; ++k) {
-          const uint32_t r = s * 256 + 4 * l + k;
-          int v = 0;
-          if (r < qlen) v = c < (uint32_t)A ? m[b->query[r] * A + c] : (int)b->S - 255;
-          h[(((size_t)s * (pad + 1) + c) * 64 + l) * 4 + k] = (int16_t)v;
-        }
-  HIPOK(b, hipSetDevice(b->device));
-  HIPOK(b, hipEventSynchronize(b->ev_ready));  // the staging buffer is free again
-  HIPOK(b, b->stage.reserve(h.size() * 2));
-  HIPOK(b, b->i32prof.reserve(h.size() / 4));
-  HIPOK(b, hipStreamWaitEvent(b->stream, b->ev_used, 0));
-  std::memcpy(b->stage.p, h.data(), h.size() * 2);
-  HIPOK(b, hipMemcpyAsync(b->i32prof.p, b->stage.p, h.size() * 2, hipMemcpyHostToDevice,
-                          b->stream));
-  HIPOK(b, hipEventRecord(b->ev_ready, b->stream));
+  if (b->pad + 1 > 25)
+    return fail(b, SW_ERR_UNSUPPORTED, "int32 kernel: alphabet %d too large", b->alpha);
+  uint32_t strips = 0;
+  const std::vector<int16_t> h =
+      qtab::build_i32(b->matrix.data(), b->alpha, (int)b->S, b->pad, b->query.data(),
+                      (uint32_t)b->query.size(), strips);
+  TableUpload up(b);
+  SWOK(up.begin(h.size() * 2));
+  SWOK(up.put(b->i32prof, h));
+  SWOK(up.end());
   b->i32_strips = strips;
   b->i32_ready = true;
   return SW_OK;
