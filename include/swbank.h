@@ -91,7 +91,9 @@ extern "C" {
  *        strands -- sw_revcomp_codes, sw_revcomp_batch_device, sw_score_strands[_device],
  *        sw_align_strand_hits[_device], SW_ALIGN_REVERSE; (test SWBANK_HAS_FRAMES) the
  *        translated search -- sw_translate_codes, sw_translate_batch_device,
- *        sw_score_frames[_device], sw_align_frame_hits[_device], SW_ALIGN_FRAME_SHIFT / _MASK. */
+ *        sw_score_frames[_device], sw_align_frame_hits[_device], SW_ALIGN_FRAME_SHIFT / _MASK;
+ *        (test SWBANK_HAS_FSHIFT) the frameshift-tolerant translated search --
+ *        sw_score_fshift[_device], SW_FSHIFT_MAX_QUERY. */
 #define SWBANK_ABI_VERSION 6
 #define SWBANK_HAS_ALIGN 1
 #define SWBANK_HAS_TOPK 1
@@ -729,7 +731,8 @@ sw_status sw_align_strand_hits(sw_bank *bank, const uint8_t *residues, size_t re
                                size_t *cigar_used);
 
 /* ---- translated search: a protein query against DNA in six reading frames (ABI 6 addition) ----
- * What the FASTA suite's tfastx does without frameshifts: every DNA target is translated in its
+ * What the FASTA suite's tfastx does without frameshifts (for a search that follows a hit across
+ * a frameshift see sw_score_fshift below): every DNA target is translated in its
  * three forward and three reverse reading frames, each frame is scored against the protein
  * query with the bank's matrix, and the best frame is kept.
  *
@@ -847,7 +850,69 @@ sw_status sw_align_frame_hits(sw_bank *bank, const uint8_t *residues, size_t res
                               const uint64_t *hits, size_t n_hits, sw_alignment *out,
                               uint32_t *cigar, size_t cigar_cap, size_t *cigar_used);
 
-/* ---- profiling (≙ the CAPI AFU's cycle counters, capi_sample_aligner/hdl-verliog/afu.v
+/* ---- frameshift-tolerant translated search: one score over the three frames of a strand (ABI 6
+ *      addition) -----------------------------------------------------------------------------
+ * The six-frame search above scores the frames as six unrelated proteins, so a single-base
+ * insertion or deletion inside a coding region (raw reads, ESTs, draft assemblies) cuts the hit
+ * in two and only the longer half is reported.  The calls below score a strand's three frames in
+ * ONE matrix whose cells may step from one frame to another at a price.  This is this library's
+ * own definition: the FASTA suite's tfasty and tfastx penalise shifts differently, and nothing
+ * in the project this one was modelled on pins it.
+ *
+ * Definition:
+ *   strand    L DNA codes c[0..L) (T, C, A, G = 0..3, N = 4).  The forward strand is the target,
+ *             the reverse strand rc(target), rc as sw_revcomp_codes.
+ *   columns   codon starts p = 0 .. L - 3.  The amino acid a(p) is the translation of c[p],
+ *             c[p + 1], c[p + 2] by the rules of the translated search above: the same
+ *             codon_table argument, any code of 4 or more gives X, * is scored like any residue.
+ *   rows      i = 0 .. m - 1 over the protein query q.
+ *   scores    with o = gap_open + gap_extend and e = gap_extend, the bank's Gotoh penalties, and
+ *             the frameshift penalty fs <= 0:
+ *               M(i,p) = s(q_i, a(p)) + max(0, H(i-1,p-3), H(i-1,p-2) + fs, H(i-1,p-4) + fs)
+ *               E(i,p) = max(H(i,p-3) + o, E(i,p-3) + e)      a codon of the target against a gap
+ *               F(i,p) = max(H(i-1,p) + o, F(i-1,p) + e)      a query residue against a gap
+ *               H(i,p) = max(0, M(i,p), E(i,p), F(i,p))
+ *             H is 0 and E, F are -infinity outside 0 <= i < m, 0 <= p <= L - 3.  The frame of a
+ *             column is p mod 3: p - 3 stays in the frame, p - 2 re-reads one base, p - 4 skips
+ *             one base.
+ *   result    the strand score is the maximum of H, 0 when L < 3; the search score is the larger
+ *             of the two strand scores; the strand output is 0 (forward) unless the reverse
+ *             strand is strictly better.
+ * While every score stays below 32,767, fs = -32767 can never win: the search then equals the
+ * merged six-frame score of sw_score_frames, and the strand is (frame >= 3).
+ *
+ * Limits: protein banks only (a DNA bank: SW_ERR_UNSUPPORTED); the Gotoh gap model only
+ * (SW_GAP_MERGED: SW_ERR_UNSUPPORTED); 0 >= frameshift >= -32767 (else SW_ERR_ARG); every query
+ * of the loaded set has at most SW_FSHIFT_MAX_QUERY rows (else SW_ERR_UNSUPPORTED).  Scores are
+ * exact int32 with no width limit.  Neither alignments nor statistics of shifted hits exist. */
+#define SWBANK_HAS_FSHIFT 1
+#define SW_FSHIFT_MAX_QUERY 1024
+
+/* Device buffers, asynchronous on `stream` (NULL = the bank's): the batch as for
+ * sw_score_frames_device (every d_lens[k] <= max_len: codes of a target past max_len are not
+ * read; a code of 5 or more reads as N).  With nq = sw_query_count(): d_scores receives the
+ * nq x n int32 search scores, query-major -- the layout sw_top_hits_device takes, so the top-k
+ * list chains on the same stream -- and d_strands (may be NULL) the nq x n uint8 strands.  One
+ * kernel reads the targets as they lie: no translation and no reverse complement is made, the
+ * call owns no scratch.  No best hit is tracked.  SW_ERR_STATE without penalties or a query;
+ * n == 0 is SW_OK; a NULL buffer (n > 0), n >= 2^32 or a table entry >= 24 is SW_ERR_ARG.  A
+ * latched hand-off fault of an earlier device call is returned as by the other device calls; a
+ * multi-device bank runs the call on its root; sw_bank_sync covers it.  sw_last_kernel reports
+ * "fshift nq=<nq> n=<n>"; with sw_bank_set_timing the call is bracketed as one launch. */
+sw_status sw_score_fshift_device(sw_bank *bank, const uint8_t *d_residues,
+                                 const uint64_t *d_offsets, const uint32_t *d_lens, size_t n,
+                                 uint32_t max_len, const uint8_t *codon_table, int32_t frameshift,
+                                 int32_t *d_scores, uint8_t *d_strands, void *stream);
+
+/* Host buffers, blocking; the batch as for sw_score_frames (a target outside the residues or a
+ * code of 5 or more is SW_ERR_ARG): uploads it once and calls the device form.  scores_out:
+ * nq x n; strands_out: nq x n, may be NULL. */
+sw_status sw_score_fshift(sw_bank *bank, const uint8_t *residues, size_t residues_len,
+                          const uint64_t *offsets, const uint32_t *lens, size_t n,
+                          const uint8_t *codon_table, int32_t frameshift, int32_t *scores_out,
+                          uint8_t *strands_out);
+
+/* ---- profiling(≙ the CAPI AFU's cycle counters, capi_sample_aligner/hdl-verliog/afu.v
  *      _DEBUGGING_ "calculation #N completed, runtime: C cycles") ------------------------- */
 /* When enabled, every launch is bracketed by hipEvents on the stream it runs on. */
 sw_status sw_bank_set_timing(sw_bank *bank, int32_t enable);

@@ -31,9 +31,12 @@ struct Pairs {
 
 size_t query_count(const sw_bank* b) { return b->qset.size() > 1 ? b->qset.size() : 1; }
 
+}  // namespace
+
 // The queries' codes and the matrix on the device, built on first use per (penalties, queries)
 // and uploaded on the bank stream like the other query tables (prepare_i32): a {offset, length}
-// entry per query, the alpha x alpha matrix, then the codes of every query back to back.
+// entry per query, the alpha x alpha matrix, then the codes of every query back to back.  The
+// frameshift search (swbank_fshift.hip) builds its profiles from the same table.
 sw_status prepare_align(sw_bank* b) {
   if (b->al_ready) return SW_OK;
   const size_t nq = query_count(b);
@@ -50,6 +53,8 @@ sw_status prepare_align(sw_bank* b) {
   b->al_ready = true;
   return SW_OK;
 }
+
+namespace {
 
 // The state every entry needs; on return the bank is prepare()d.  The single-query entries
 // refuse a loaded set.

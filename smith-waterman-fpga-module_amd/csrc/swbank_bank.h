@@ -8,7 +8,8 @@
 // every row of a score matrix, the best query of every column), swbank_stat.hip (hit
 // statistics: the seeded shuffle, the score histogram, the estimate, bits and E-values),
 // swbank_strand.hip (both DNA strands: the reverse complement, the strand-merged scores),
-// swbank_frame.hip (the translated search: six-frame translation, frame-merged scores).
+// swbank_frame.hip (the translated search: six-frame translation, frame-merged scores),
+// swbank_fshift.hip (the frameshift-tolerant translated search: one kernel over three frames).
 //
 // This header also holds what those units share: the buffer types, which free themselves with
 // the bank (DevBuf, UcBuf, PinBuf), the sliced scratch and the staged host batch (SliceScratch,
@@ -165,6 +166,17 @@ extern "C" hipError_t swk_frame_fixup(sw_alignment* out, const uint32_t* lens, c
                                       size_t n, size_t nq, const uint8_t* frames,
                                       const uint32_t* hit_queries, size_t hits_per_query,
                                       const uint64_t* hits, size_t n_hits, hipStream_t st);
+// swbank_kfshift.hip: the three-frame score kernel of the frameshift-tolerant translated search
+// (qtab / mat / query: al_tab's parts; qlen: the longest query, at most SW_FSHIFT_MAX_QUERY;
+// table: 64 protein codes on the host; o = open + extend, e, fs <= 0; scores and strands
+// (optional) nq x n) and the rows a lane holds for that qlen
+extern "C" int swk_fshift_rows(uint32_t qlen);
+extern "C" hipError_t swk_fshift_score(const uint8_t* res, const uint64_t* offs,
+                                       const uint32_t* lens, size_t n, uint32_t max_len,
+                                       const uint2* qtab, const int8_t* mat, const uint8_t* query,
+                                       size_t nq, uint32_t qlen, uint32_t alpha,
+                                       const uint8_t* table, int32_t o, int32_t e, int32_t fs,
+                                       int32_t* scores, uint8_t* strands, hipStream_t st);
 extern "C" hipError_t swk_stat_signif(const double* par, const int32_t* hit_scores,
                                       const uint64_t* hits, const uint32_t* lens, size_t k,
                                       size_t nq, double db_size, double* bits, double* evalues,
@@ -995,6 +1007,8 @@ sw_status multi_device(sw_bank* b, const uint8_t* d_res, const uint64_t* d_offs,
 // scored in place, only the int32 scores gathered to the root into d_gathered (may be null).
 sw_status multi_resident(sw_bank* b, const sw_device_batch* per, int32_t* d_gathered,
                          hipStream_t hs);
+// ---- swbank_align.hip: the queries' codes and the matrix on the device (al_tab), after prepare()
+sw_status prepare_align(sw_bank* b);
 // ---- swbank_launch.hip (device batches against a query set; sstride: between query rows)
 sw_status launch_set(sw_bank* b, const uint8_t* d_res, const uint64_t* d_offs,
                      const uint32_t* d_lens, size_t n, uint32_t min_len, uint32_t max_len,

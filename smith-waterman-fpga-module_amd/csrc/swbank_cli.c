@@ -9,7 +9,7 @@
  *
  * Usage: swbank -q query.fa -l library.fa [-p match,mismatch,open,extend] [-P] [-g]
  *               [-d device[,device...]] [-o out.txt] [-T] [-R scores.txt] [-b] [-A k]
- *               [-E rounds[,seed]] [-S lambda,K] [-B] [-X]
+ *               [-E rounds[,seed]] [-S lambda,K] [-B] [-X [-F frameshift]]
  *   -p  penalties (default 5,-4,-12,-4: ScoreBank_v1_tb.sv:16-19, data/smith-waterman.py:6-10)
  *   -P  protein mode (BLOSUM62; -p gives only open,extend)      -g  Gotoh gap model
  *   -T  testbench transcript format "@     0ns: %10s score: \t%d"
@@ -52,6 +52,14 @@
  *       on shuffles of the library's six translations (made here with sw_translate_codes and
  *       handed to sw_estimate_statistics as the protein batch they are).  Not with -B (the
  *       reverse frames are already searched).
+ *   -F  with -X: the frameshift-tolerant search (sw_score_fshift; this library's own definition,
+ *       include/swbank.h): the three frames of a strand are scored in one matrix whose cells may
+ *       step to another frame (one base re-read or skipped) at the price `frameshift`, 0 to
+ *       -32767, so a hit is followed across a single-base insertion or deletion.  Every score is
+ *       the better strand's and " [f]" or " [r]" (the reverse strand strictly better) follows
+ *       it, as with -B.  The call knows the Gotoh gap model only, so -F implies -g.  Alignments
+ *       and statistics of shifted hits do not exist yet: not with -A, -E or -S; and not with -B
+ *       (both strands are searched already).
  *   -b  also print the bank's best hit ("best: >name score: S", ≙ max / vld_max) to stderr
  * FASTA: '>' starts a record (name = first token); sequence lines are concatenated; CR/LF,
  * blank lines and lower case are accepted; bytes outside the alphabet encode to N (DNA) or X
@@ -140,8 +148,10 @@ static void usage(const char *argv0) {
   fprintf(stderr,
           "usage: %s -q query.fa -l library.fa [-p match,mismatch,open,extend] [-P] [-g]\n"
           "          [-d device[,device...]] [-o out.txt] [-T] [-R scores.txt] [-b] [-A k]\n"
-          "          [-E rounds[,seed]] [-S lambda,K] [-B] [-X]\n"
-          "  -X: protein query against a DNA library in six reading frames; not with -B\n",
+          "          [-E rounds[,seed]] [-S lambda,K] [-B] [-X [-F frameshift]]\n"
+          "  -X: protein query against a DNA library in six reading frames; not with -B\n"
+          "  -F: with -X, follow hits across frameshifts at this penalty (0 .. -32767; implies -g);\n"
+          "      not with -A, -E, -S or -B\n",
           argv0);
 }
 
@@ -247,14 +257,14 @@ static int print_alignments(FILE *out, sw_bank *bank, const uint8_t *res, size_t
 int main(int argc, char **argv) {
   const char *qpath = NULL, *lpath = NULL, *opath = NULL, *pen = NULL, *rpath = NULL;
   int protein = 0, gotoh = 0, device = -1, transcript = 0, best = 0, both = 0, xlate = 0, opt;
-  int ndev = 0, devs[SW_MAX_DEVICES];
-  long nalign = 0;
+  int ndev = 0, devs[SW_MAX_DEVICES], fshift = 0;
+  long nalign = 0, fs = 0;
   int have_stats = 0; /* 1: -S (given), 2: -E (estimated) */
   unsigned long stat_rounds = 0;
   unsigned long long stat_seed = 0;
   sw_statistics stats;
   memset(&stats, 0, sizeof(stats));
-  while ((opt = getopt(argc, argv, "q:l:p:Pgd:o:TR:bA:E:S:BXh")) != -1) {
+  while ((opt = getopt(argc, argv, "q:l:p:Pgd:o:TR:bA:E:S:BXF:h")) != -1) {
     switch (opt) {
       case 'q': qpath = optarg; break;
       case 'l': lpath = optarg; break;
@@ -277,6 +287,16 @@ int main(int argc, char **argv) {
       case 'b': best = 1; break;
       case 'B': both = 1; break;
       case 'X': xlate = protein = 1; break;
+      case 'F': {
+        char *end;
+        fs = strtol(optarg, &end, 10);
+        if (end == optarg || *end || fs > 0 || fs < -32767) {
+          fprintf(stderr, "-F takes a frameshift penalty of 0 to -32767\n");
+          return usage(argv[0]), 1;
+        }
+        fshift = gotoh = 1;
+        break;
+      }
       case 'A': {
         char *end;
         nalign = strtol(optarg, &end, 10);
@@ -312,6 +332,19 @@ int main(int argc, char **argv) {
     fprintf(stderr, "Input files missing\n");
     usage(argv[0]);
     return 1;
+  }
+  if (fshift) {
+    const char *why =
+        !xlate       ? "-F is the frameshift penalty of the translated search: it needs -X"
+        : nalign > 0 ? "-F: alignments of shifted hits do not exist yet: not with -A"
+        : have_stats ? "-F: statistics of shifted scores do not exist yet: not with -E or -S"
+        : both       ? "-F searches both strands already: not with -B"
+                     : NULL;
+    if (why) {
+      fprintf(stderr, "%s\n", why);
+      usage(argv[0]);
+      return 1;
+    }
   }
   if (xlate && both) {
     fprintf(stderr, "-X searches the reverse frames already: not with -B\n");
@@ -377,9 +410,10 @@ int main(int argc, char **argv) {
   uint64_t *offs = malloc((lib.n + 1) * sizeof(uint64_t));
   uint32_t *lens = malloc((lib.n + 1) * sizeof(uint32_t));
   int32_t *scores = malloc((lib.n + 1) * sizeof(int32_t));
-  uint8_t *strands = both ? calloc(lib.n + 1, 1) : NULL;
-  uint8_t *frames = xlate ? calloc(lib.n + 1, 1) : NULL;
-  if (!res || !offs || !lens || !scores || (both && !strands) || (xlate && !frames))
+  uint8_t *strands = both || fshift ? calloc(lib.n + 1, 1) : NULL;
+  uint8_t *frames = xlate && !fshift ? calloc(lib.n + 1, 1) : NULL;
+  if (!res || !offs || !lens || !scores || ((both || fshift) && !strands) ||
+      (xlate && !fshift && !frames))
     st = SW_ERR_NOMEM;
   size_t pos = 0;
   for (size_t k = 0; st == SW_OK && k < lib.n; ++k) {
@@ -390,7 +424,9 @@ int main(int argc, char **argv) {
     pos += l;
   }
   if (st == SW_OK)
-    st = xlate  ? sw_score_frames(bank, res, total, offs, lens, lib.n, NULL, scores, frames)
+    st = fshift ? sw_score_fshift(bank, res, total, offs, lens, lib.n, NULL, (int32_t)fs, scores,
+                                  strands)
+         : xlate ? sw_score_frames(bank, res, total, offs, lens, lib.n, NULL, scores, frames)
          : both ? sw_score_strands(bank, res, total, offs, lens, lib.n, scores, strands)
                 : sw_score_batch(bank, res, total, offs, lens, NULL, lib.n, scores);
   if (st == SW_OK && have_stats == 2 && lib.n && xlate) {
@@ -432,9 +468,9 @@ int main(int argc, char **argv) {
   for (size_t k = 0; k < lib.n; ++k) {
     char nm[256];
     snprintf(nm, sizeof(nm), ">%s", lib.names[k]);
-    const char *sd = xlate  ? kFrameTag[frames[k] < SW_FRAME_COUNT ? frames[k] : 0]
-                     : both ? (strands[k] ? " [r]" : " [f]")
-                            : "";
+    const char *sd = strands ? (strands[k] ? " [r]" : " [f]") /* -B, -X -F */
+                     : xlate ? kFrameTag[frames[k] < SW_FRAME_COUNT ? frames[k] : 0]
+                             : "";
     if (transcript)
       fprintf(out, "@%6dns: %10s score: \t%10d%s\n", 0, nm, scores[k], sd);
     else
@@ -460,9 +496,9 @@ int main(int argc, char **argv) {
       (both || xlate ? sw_best_hit(bank, scores, NULL, lib.n, &bid, &bsc)
                      : sw_batch_best(bank, &bid, &bsc, NULL)) == SW_OK)
     fprintf(stderr, "best: >%s score: %d%s\n", lib.names[bid], bsc,
-            xlate  ? kFrameTag[frames[bid] < SW_FRAME_COUNT ? frames[bid] : 0]
-            : both ? (strands[bid] ? " [r]" : " [f]")
-                   : "");
+            strands ? (strands[bid] ? " [r]" : " [f]")
+            : xlate ? kFrameTag[frames[bid] < SW_FRAME_COUNT ? frames[bid] : 0]
+                    : "");
   if (rpath) { /* ssearch36 -R layout (data/score500.txt:1-3,502-503) */
     FILE *rf = fopen(rpath, "w");
     if (!rf) {

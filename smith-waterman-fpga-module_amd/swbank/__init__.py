@@ -56,6 +56,7 @@ EXPORTS = (
     "sw_score_strands_device", "sw_align_strand_hits", "sw_align_strand_hits_device",
     "sw_translate_codes", "sw_translate_batch_device", "sw_score_frames",
     "sw_score_frames_device", "sw_align_frame_hits", "sw_align_frame_hits_device",
+    "sw_score_fshift", "sw_score_fshift_device",
 )
 ABI_VERSION = 6
 COUNTERS = ("stream_calls", "stream_reruns", "stream_declined", "chunked_calls", "device_sorts",
@@ -71,6 +72,7 @@ ALIGN_FRAME_SHIFT, ALIGN_FRAME_MASK = 4, 0x30  # ... f % 3 of a translated hit's
 _ALIGN_WHERE = ALIGN_REVERSE | ALIGN_FRAME_MASK  # (flags that say where a hit lies, not how)
 FRAME_COUNT = 6                              # SW_FRAME_COUNT: reading frames of a DNA target
 FRAME_TAGS = ("+1", "+2", "+3", "-1", "-2", "-3")
+FSHIFT_MAX_QUERY = 1024                      # SW_FSHIFT_MAX_QUERY: query rows of score_frameshift
 STANDARD_CODE = "FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG"
 RECORD_BYTES, RECORD_MAX_BASES = 64, 232
 TOP_MAX_K = 4096                             # SW_TOP_MAX_K: the largest k of the top-hits calls
@@ -287,6 +289,8 @@ def lib() -> ctypes.CDLL:
         "sw_align_frame_hits": (i32, [P, P, sz, P, P, P, sz, P, P, P, sz, P, sz, P, P, sz, P]),
         "sw_align_frame_hits_device": (i32, [P, P, P, P, P, sz, u32, P, P, P, sz, P, sz, P, P, u32,
                                              P]),
+        "sw_score_fshift": (i32, [P, P, sz, P, P, sz, P, i32, P, P]),
+        "sw_score_fshift_device": (i32, [P, P, P, P, sz, u32, P, i32, P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -956,6 +960,38 @@ class ScoreBank:
         scores = sc[:nq * n].reshape(nq, n)
         frames = fr[:nq * n].reshape(nq, n)
         return (scores[0], frames[0]) if nq == 1 else (scores, frames)
+
+    # the frameshift-tolerant translated search: one score over the three frames of a strand
+    def score_frameshift_device(self, d_dna: int, d_offs: int, d_lens: int, n: int, max_len: int,
+                                frameshift: int, d_scores: int, d_strands: int = 0,
+                                codon_table=None, stream: int = 0):
+        """sw_score_fshift_device: device pointers (ints); d_scores receives the nq x n int32
+        scores of the DNA batch against the protein queries under the frameshift penalty
+        `frameshift` (0 .. -32767), d_strands (optional) the nq x n uint8 strands (1: the reverse
+        strand is strictly better).  Async on `stream`."""
+        tab = _codon_table(codon_table)
+        self._check(lib().sw_score_fshift_device(
+            self._h, d_dna or None, d_offs or None, d_lens or None, n, max_len,
+            _p(tab) if tab is not None else None, frameshift, d_scores or None, d_strands or None,
+            stream or None))
+
+    def score_frameshift(self, targets, frameshift: int, codon_table=None):
+        """sw_score_fshift: (scores int32, strands uint8) of host DNA targets, [n] for one loaded
+        query, [nq, n] for a query set.  `targets`: a sequence of DNA code arrays, or a packed
+        batch as the tuple (residues, offsets, lens)."""
+        if not (isinstance(targets, tuple) and len(targets) == 3):
+            targets = pack_targets([np.asarray(t, np.uint8) for t in targets])
+        res, offs, ln, _ = validate_batch(*targets)
+        tab = _codon_table(codon_table)
+        nq, n = max(self.query_count(), 1), len(ln)
+        sc = np.zeros(nq * max(n, 1), np.int32)
+        sd = np.zeros(nq * max(n, 1), np.uint8)
+        self._check(lib().sw_score_fshift(self._h, _p(res), res.size, _p(offs), _p(ln), n,
+                                          _p(tab) if tab is not None else None, frameshift,
+                                          _p(sc), _p(sd)))
+        scores = sc[:nq * n].reshape(nq, n)
+        strands = sd[:nq * n].reshape(nq, n)
+        return (scores[0], strands[0]) if nq == 1 else (scores, strands)
 
     def align_frame_hits(self, residues: np.ndarray, offsets: np.ndarray, lens: np.ndarray,
                          frames, hits=None, hit_queries=None, hits_per_query: int = 0,
