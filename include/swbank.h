@@ -93,7 +93,8 @@ extern "C" {
  *        translated search -- sw_translate_codes, sw_translate_batch_device,
  *        sw_score_frames[_device], sw_align_frame_hits[_device], SW_ALIGN_FRAME_SHIFT / _MASK;
  *        (test SWBANK_HAS_FSHIFT) the frameshift-tolerant translated search --
- *        sw_score_fshift[_device], SW_FSHIFT_MAX_QUERY. */
+ *        sw_score_fshift[_device], SW_FSHIFT_MAX_QUERY; (test SWBANK_HAS_FSHIFT_ALIGN) alignments
+ *        of frameshift hits -- sw_align_fshift_hits[_device], SW_CIGAR_FS_SKIP / _BACK. */
 #define SWBANK_ABI_VERSION 6
 #define SWBANK_HAS_ALIGN 1
 #define SWBANK_HAS_TOPK 1
@@ -884,7 +885,8 @@ sw_status sw_align_frame_hits(sw_bank *bank, const uint8_t *residues, size_t res
  * Limits: protein banks only (a DNA bank: SW_ERR_UNSUPPORTED); the Gotoh gap model only
  * (SW_GAP_MERGED: SW_ERR_UNSUPPORTED); 0 >= frameshift >= -32767 (else SW_ERR_ARG); every query
  * of the loaded set has at most SW_FSHIFT_MAX_QUERY rows (else SW_ERR_UNSUPPORTED).  Scores are
- * exact int32 with no width limit.  Neither alignments nor statistics of shifted hits exist. */
+ * exact int32 with no width limit.  Alignments of shifted hits: sw_align_fshift_hits[_device]
+ * below; statistics of shifted hits do not exist. */
 #define SWBANK_HAS_FSHIFT 1
 #define SW_FSHIFT_MAX_QUERY 1024
 
@@ -911,6 +913,83 @@ sw_status sw_score_fshift(sw_bank *bank, const uint8_t *residues, size_t residue
                           const uint64_t *offsets, const uint32_t *lens, size_t n,
                           const uint8_t *codon_table, int32_t frameshift, int32_t *scores_out,
                           uint8_t *strands_out);
+
+/* ---- alignments of frameshift hits (ABI 6 addition) ---------------------------------------------
+ * Where a hit of the frameshift-tolerant search lies and where it changes frame: the step that
+ * follows sw_score_fshift_device -> sw_top_hits_device on the same stream.  The pair list is that
+ * of sw_align_set_hits (hit_queries or hits_per_query, hits or h itself, the SW_QUERY_NONE /
+ * SW_HIT_NONE sentinels).  The call takes no strand matrix: it scores both strands itself.
+ *
+ * Everything is defined on the hit's strand c[0..L), the target or rc(target), over the matrices
+ * M, E, F, H of the definition above; a cell is (i, p), query row i and codon start p.
+ *   score   what sw_score_fshift returns for the pair; the forward strand unless the reverse
+ *           strand is strictly better (then flags |= SW_ALIGN_REVERSE).
+ *   end     among the cells with H = score: the smallest p, then the smallest i.  The end cell is
+ *           walked as an M cell.
+ *   start   among the first cells of optimal alignments that end there: the largest p, then the
+ *           largest i -- the same rule on the reversed problem (rows q[q_end..0], columns
+ *           p_end..0, each column keeping its forward codon): between two consecutive match
+ *           cells the forward and the reversed recurrence consume the same bases and pay the same
+ *           penalties, only the gap cells move by a base.
+ *   CIGAR   an op is len << 4 | code, adjacent equal codes merged, the first and the last op M.
+ *           SW_CIGAR_M, _I, _D as in the translated search: amino-acid columns, a D consumes one
+ *           codon.  Two more codes, always of length 1, each directly before the M run it leads
+ *           into: SW_CIGAR_FS_SKIP, text '/': the next codon starts one base later than the frame
+ *           says (the p - 4 link); SW_CIGAR_FS_BACK, text '\': it starts one base earlier,
+ *           re-reading a base (the p - 2 link).  The ops consume (M + I) = q_end - q_start + 1
+ *           query rows and 3 (M + D) + (count of '/') - (count of '\') = p_end + 2 - p_start + 1
+ *           bases; re-scoring them gives `score`: an M scores s(q_i, a(p)), a gap run of k
+ *           columns costs open + k * extend, a shift costs `frameshift`.  n_columns = M + I + D
+ *           columns, n_identities = M columns with q_i == a(p).  The path is optimal among the
+ *           paths from the start cell to the end cell, values taken in that anchored matrix (a 0
+ *           diagonal at the start cell only, no floor).  Walking back from the end cell: in state
+ *           H, M first, then E (D), then F (I); in an M cell the in-frame link p - 3, then p - 2
+ *           ('\'), then p - 4 ('/'); a gap run opens rather than extends when both are optimal.
+ *   record  index and id name the DNA target; flags |= (p_start mod 3) << SW_ALIGN_FRAME_SHIFT,
+ *           the frame of the first codon on its strand; t_start and t_end are nucleotide positions
+ *           on the forward target, 0-based, inclusive:
+ *             forward   t_start = p_start,                 t_end = p_end + 2
+ *             reverse   t_start = L - 1 - (p_end + 2),     t_end = L - 1 - p_start
+ *           q_* are query rows.  The empty pair (score 0, L < 3 included) is SW_ALIGN_EMPTY: every
+ *           coordinate 0, no ops, no strand or frame bits.
+ * SW_ALIGN_NO_PATH (exact coordinates, no ops, n_columns = n_identities = 0), the SW_ALIGN_NO_HIT
+ * sentinel slots, the cigar_offset = h * cigar_stride device layout, the packed host layout and
+ * the SWBANK_ALIGN_MB budget with its chunks are those of sw_align_set_hits.  While scores stay
+ * below 32,767 and one frame of the six is strictly best, the record at frameshift = -32767 equals
+ * the record of sw_align_frame_hits for that frame, field for field and op for op.
+ *
+ * Limits and refusals are sw_score_fshift's, in its order: protein banks, the Gotoh model, the
+ * frameshift range, the codon table, the state, queries of at most SW_FSHIFT_MAX_QUERY rows; then
+ * max_len (the host form: the longest listed target) of less than 2^29, else SW_ERR_UNSUPPORTED.  A
+ * latched hand-off fault is returned as elsewhere; a multi-device bank runs the call on its root.
+ * sw_last_kernel reports "align-fshift i32 nq=<nq> hits=<n_hits> chunks=<c>"; with
+ * sw_bank_set_timing the end / start passes and the path passes are bracketed as one launch each.
+ * One workgroup aligns one hit, with K = 4, 8 or 16 rows per lane by the longest loaded query; a
+ * window of r rows and c codon starts takes (ceil(c / 3) + ceil(r / K) - 1) x 192 K bytes of the
+ * direction store. */
+#define SWBANK_HAS_FSHIFT_ALIGN 1
+enum { SW_CIGAR_FS_SKIP = 3, SW_CIGAR_FS_BACK = 4 };
+
+/* Device buffers, asynchronous on `stream`: as sw_align_frame_hits_device without the frames.  The
+ * slots of the direction store are sized from max_len x the longest query; if one does not fit
+ * SWBANK_ALIGN_MB, every non-empty hit gets SW_ALIGN_NO_PATH. */
+sw_status sw_align_fshift_hits_device(sw_bank *bank, const uint8_t *d_residues,
+                                      const uint64_t *d_offsets, const uint32_t *d_lens,
+                                      const uint64_t *d_ids, size_t n, uint32_t max_len,
+                                      const uint8_t *codon_table, int32_t frameshift,
+                                      const uint32_t *d_hit_queries, size_t hits_per_query,
+                                      const uint64_t *d_hits, size_t n_hits, sw_alignment *d_out,
+                                      uint32_t *d_cigar, uint32_t cigar_stride, void *stream);
+
+/* Host buffers, blocking: gathers and uploads only the listed targets (a code of 5 or more in one
+ * is SW_ERR_ARG) and plans its chunks from the actual windows after one small copy of the
+ * coordinates back, so only a single window over the budget loses its path. */
+sw_status sw_align_fshift_hits(sw_bank *bank, const uint8_t *residues, size_t residues_len,
+                               const uint64_t *offsets, const uint32_t *lens, const uint64_t *ids,
+                               size_t n, const uint8_t *codon_table, int32_t frameshift,
+                               const uint32_t *hit_queries, size_t hits_per_query,
+                               const uint64_t *hits, size_t n_hits, sw_alignment *out,
+                               uint32_t *cigar, size_t cigar_cap, size_t *cigar_used);
 
 /* ---- profiling(≙ the CAPI AFU's cycle counters, capi_sample_aligner/hdl-verliog/afu.v
  *      _DEBUGGING_ "calculation #N completed, runtime: C cycles") ------------------------- */
@@ -985,7 +1064,8 @@ size_t sw_pack_2bit(const char *ascii, size_t n, uint8_t *out);
 size_t sw_unpack_2bit(const uint8_t *packed, size_t n, uint8_t *codes);
 /* Fill a substitution matrix: DNA (alpha 5) from match/mismatch, or BLOSUM62 (alpha 24). */
 sw_status sw_fill_matrix(int32_t alphabet, int32_t match, int32_t mismatch, int8_t *matrix);
-/* CIGAR ops -> text, e.g. "15M2I17M4D13M" (an op code past D prints as '?'): writes at most
+/* CIGAR ops -> text, e.g. "15M2I17M4D13M" or "20M1/20M" (SW_CIGAR_FS_SKIP prints as '/',
+ * SW_CIGAR_FS_BACK as '\', any other op code past D as '?'): writes at most
  * cap - 1 characters and a NUL into buf (nothing when cap == 0; buf may then be NULL) and
  * returns the length the whole string needs, excluding the NUL. */
 size_t sw_cigar_string(const uint32_t *ops, size_t n_ops, char *buf, size_t cap);

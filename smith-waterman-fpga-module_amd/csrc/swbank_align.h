@@ -64,6 +64,43 @@ hipError_t swk_launch_align_paths(const SwkAlign* p, const uint32_t* list, size_
                                   hipStream_t st);
 /* After the paths of a strand call: SW_ALIGN_REVERSE and forward target coordinates. */
 hipError_t swk_launch_align_flip(const SwkAlign* p, hipStream_t st);
+
+/* Alignments of frameshift hits (swbank_kfsalign.hip): one call's arguments.  The
+ * batch holds DNA; hit h is query hit_queries[h], or h / hits_per_query, of the nq queries of
+ * qtab (at most qlen <= 1024 rows each) against target hits[h], or h, of n; a hit whose query is
+ * >= nq or whose target is >= n names no pair.  table: 64 protein codes; o = open + extend, e,
+ * fs <= 0. */
+typedef struct SwkFsAlign {
+  const uint8_t* res;
+  const uint64_t* offs;
+  const uint32_t* lens;
+  const uint64_t* ids;
+  const uint64_t* hits;
+  size_t n_hits, n;
+  uint32_t max_len; /* codes of a target past it are not read */
+  const uint2* qtab;
+  const int8_t* mat;
+  const uint8_t* query;
+  uint32_t nq, qlen, alpha;
+  const uint32_t* hit_queries;
+  uint32_t hits_per_query;
+  uint8_t table[64];
+  int32_t o, e, fs;
+  void* out; /* sw_alignment[n_hits] */
+  uint32_t* cigar;
+  uint32_t cigar_stride;
+} SwkFsAlign;
+
+/* Dwords of direction store a window of rows x cols cells (cols codon starts) takes under the
+ * rows per lane K of queries of at most qlen rows: (ceil(cols / 3) + ceil(rows / K) - 1) steps x
+ * 3K bytes x 64 lanes. */
+uint64_t swk_fsalign_dir_dwords(uint32_t qlen, uint32_t rows, uint32_t cols);
+/* Passes A and B for hits [0, n_hits): every record written, paths left out. */
+hipError_t swk_launch_fsalign_ends(const SwkFsAlign* p, hipStream_t st);
+/* Passes C and D for `count` positions, placed as swk_launch_align_paths places them. */
+hipError_t swk_launch_fsalign_paths(const SwkFsAlign* p, const uint32_t* list, size_t h0,
+                                    size_t count, const SwkAlignPlan* plan, uint64_t slot,
+                                    uint32_t* dirs, hipStream_t st);
 #ifdef __cplusplus
 }
 #endif

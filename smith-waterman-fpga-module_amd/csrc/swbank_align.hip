@@ -3,7 +3,8 @@
 // (sw_align_set_hits*), and for a set with a strand per pair (sw_align_strand_hits*, DESIGN.md
 // §3.13), the chunking of the direction store, the host calls' staging.  All entries run the same
 // code; they differ in the pair list.  The kernels are in
-// swbank_kalign.hip.
+// swbank_kalign.hip.  The alignments of frameshift hits (sw_align_fshift_hits*, DESIGN.md §3.16,
+// at the end of the file) run the same scaffolding around the kernels of swbank_kfsalign.hip.
 #include "swbank_bank.h"
 
 namespace {
@@ -155,19 +156,28 @@ bool align_opening(sw_bank* b, const Pairs& pr, void* stream, sw_status& st, F&&
 
 // Passes C and D of a device call in slots of the largest possible window (nothing is read
 // back); a window past the budget: every non-empty hit keeps SW_ALIGN_NO_PATH.
-sw_status paths_by_slot(sw_bank* b, const SwkAlign& p, uint32_t max_len, hipStream_t hs,
-                        size_t& chunks) {
-  const uint64_t slot = swk_align_dir_dwords(p.qlen, max_len), budget = dir_budget();
+// launch(h0, count): passes C and D of hits [h0, h0 + count) in slots of `slot` dwords of al_dirs.
+template <class Launch>
+sw_status paths_in_slots(sw_bank* b, size_t n_hits, uint64_t slot, hipStream_t hs, size_t& chunks,
+                         Launch&& launch) {
+  const uint64_t budget = dir_budget();
   const size_t per =
-      slot == 0 || slot > budget ? 0 : (size_t)std::min<uint64_t>(budget / slot, p.n_hits);
+      slot == 0 || slot > budget ? 0 : (size_t)std::min<uint64_t>(budget / slot, n_hits);
   if (per) HIPOK(b, b->al_dirs.reserve((size_t)(slot * per)));
   return timed_on(b, hs, [&] {
-    for (size_t h0 = 0; per && h0 < p.n_hits; h0 += per, ++chunks) {
-      const hipError_t e = swk_launch_align_paths(&p, nullptr, h0, std::min(per, p.n_hits - h0),
-                                                  nullptr, slot, b->al_dirs.p, hs);
+    for (size_t h0 = 0; per && h0 < n_hits; h0 += per, ++chunks) {
+      const hipError_t e = launch(h0, std::min(per, n_hits - h0));
       if (e != hipSuccess) return e;
     }
     return hipSuccess;
+  });
+}
+
+sw_status paths_by_slot(sw_bank* b, const SwkAlign& p, uint32_t max_len, hipStream_t hs,
+                        size_t& chunks) {
+  const uint64_t slot = swk_align_dir_dwords(p.qlen, max_len);
+  return paths_in_slots(b, p.n_hits, slot, hs, chunks, [&](size_t h0, size_t count) {
+    return swk_launch_align_paths(&p, nullptr, h0, count, nullptr, slot, b->al_dirs.p, hs);
   });
 }
 
@@ -288,8 +298,10 @@ sw_status gather_hits(sw_bank* b, const uint8_t* residues, size_t residues_len,
 }
 
 // Step 2: the gathered batch on the device (hit h is target h against query al_hq[h], on strand
-// al_hs[h]) and the launch block over it.
-sw_status stage_hits(sw_bank* b, const Pairs& pr, const Gathered& g, SwkAlign& p, hipStream_t hs) {
+// al_hs[h]) and, with `block`, the launch block of the alignment kernels over it (its scratch
+// rows included; the frameshift kernels have none and take the staged buffers alone).
+sw_status stage_hits(sw_bank* b, const Pairs& pr, const Gathered& g, SwkAlign& p, hipStream_t hs,
+                     bool block = true) {
   const size_t n_hits = pr.n_hits;
   HIPOK(b, b->al_res.reserve(g.res.size()));
   HIPOK(b, b->al_offs.reserve(n_hits));
@@ -321,7 +333,7 @@ sw_status stage_hits(sw_bank* b, const Pairs& pr, const Gathered& g, SwkAlign& p
     p.strands = b->al_hs.p;
     p.strand_by_hit = 1;
   }
-  return align_block(b, p, n_hits, g.max_len);
+  return block ? align_block(b, p, n_hits, g.max_len) : SW_OK;
 }
 
 // Step 3: the CIGAR windows of pass A's records that fit the budget (dwords of direction store),
@@ -334,14 +346,16 @@ struct Windows {
   uint64_t most = 0, cig = 0;      // the largest chunk's dwords; ops slots in all
 };
 
-Windows plan_windows(const sw_alignment* out, size_t n_hits, uint64_t budget) {
+// dwords(Q, L): what a window of Q query rows and L target codes takes.
+template <class D>
+Windows plan_windows(const sw_alignment* out, size_t n_hits, uint64_t budget, D&& dwords) {
   Windows w;
   uint64_t used = 0;
   for (size_t h = 0; h < n_hits; ++h) {
     const sw_alignment& r = out[h];
     if (r.score <= 0) continue;
     const uint32_t Q = r.q_end - r.q_start + 1, L = r.t_end - r.t_start + 1;
-    const uint64_t need = swk_align_dir_dwords(Q, L);
+    const uint64_t need = dwords(Q, L);
     if (need > budget) continue;  // SW_ALIGN_NO_PATH, coordinates stay
     if (used + need > budget) {
       w.cut.push_back(w.list.size());
@@ -367,9 +381,10 @@ size_t pack_ops(const Windows& w, const std::vector<uint32_t>& ops, sw_alignment
     const uint64_t from = planned ? w.plan[k].cig_off : 0;
     if (planned) ++k;
     r.cigar_offset = 0;
-    if (r.flags != 0 || !planned) continue;
+    // (a frameshift record carries its strand and frame bits already)
+    if ((r.flags & (SW_ALIGN_EMPTY | SW_ALIGN_NO_PATH | SW_ALIGN_NO_HIT)) || !planned) continue;
     if (r.cigar_len > cigar_cap - at) {
-      r.flags = SW_ALIGN_NO_PATH;
+      r.flags |= SW_ALIGN_NO_PATH;
       r.cigar_len = r.n_columns = r.n_identities = 0;
       continue;
     }
@@ -400,6 +415,61 @@ void rewrite_records(const Pairs& pr, const Gathered& g, const uint64_t* ids, bo
   }
 }
 
+// What a host call does once its hits are staged, whichever kernels it runs: ends(hs) launches
+// passes A and B over the staged hits (records at al_out); paths(list, count, plan, hs) launches
+// passes C and D of one chunk (ops at al_cig by the plan, directions at al_dirs); dwords(Q, L) is
+// the direction store of a window.  The records and the packed ops go to the caller's buffers.
+template <class Ends, class Paths, class Dwords>
+sw_status host_passes(sw_bank* b, const Pairs& pr, const Gathered& g, const uint64_t* ids,
+                      hipStream_t hs, Ends&& ends, Paths&& paths, Dwords&& dwords,
+                      sw_alignment* out, uint32_t* cigar, size_t cigar_cap, size_t* cigar_used,
+                      size_t& chunks) {
+  const size_t n_hits = pr.n_hits;
+  sw_status st;
+  // passes A and B, the records back
+  if ((st = timed_on(b, hs, [&] { return ends(hs); })) != SW_OK) return st;
+  HIPOK(b, hipMemcpyAsync(out, b->al_out.p, n_hits * sizeof(sw_alignment), hipMemcpyDeviceToHost,
+                          hs));
+  HIPOK(b, hipStreamSynchronize(hs));
+  cigar_cap = std::min<size_t>(cigar_cap, 0xFFFFFFFFu);  // (cigar_offset is 32 bits)
+  const bool with_cigar = cigar && cigar_cap;
+  if (with_cigar) {
+    const Windows w = plan_windows(out, n_hits, dir_budget(), dwords);
+    std::vector<uint32_t> ops;
+    if (!w.list.empty()) {  // passes C and D chunk by chunk, the records and the ops back
+      HIPOK(b, b->al_dirs.reserve((size_t)w.most));
+      HIPOK(b, b->al_cig.reserve((size_t)w.cig));
+      HIPOK(b, b->al_list.reserve(w.list.size()));
+      HIPOK(b, b->al_plan.reserve(w.plan.size()));
+      HIPOK(b, hipMemcpyAsync(b->al_list.p, w.list.data(), w.list.size() * 4,
+                              hipMemcpyHostToDevice, hs));
+      HIPOK(b, hipMemcpyAsync(b->al_plan.p, w.plan.data(), w.plan.size() * sizeof(SwkAlignPlan),
+                              hipMemcpyHostToDevice, hs));
+      st = timed_on(b, hs, [&] {
+        for (size_t c = 0; c + 1 < w.cut.size(); ++c) {
+          if (w.cut[c + 1] == w.cut[c]) continue;
+          const hipError_t e = paths(b->al_list.p + w.cut[c], w.cut[c + 1] - w.cut[c],
+                                     b->al_plan.p + w.cut[c], hs);
+          if (e != hipSuccess) return e;
+          ++chunks;
+        }
+        return hipSuccess;
+      });
+      if (st != SW_OK) return st;
+      ops.resize((size_t)w.cig);
+      HIPOK(b, hipMemcpyAsync(out, b->al_out.p, n_hits * sizeof(sw_alignment),
+                              hipMemcpyDeviceToHost, hs));
+      HIPOK(b, hipMemcpyAsync(ops.data(), b->al_cig.p, ops.size() * 4, hipMemcpyDeviceToHost, hs));
+      HIPOK(b, hipStreamSynchronize(hs));
+    }
+    const size_t used = pack_ops(w, ops, out, n_hits, cigar, cigar_cap);
+    if (cigar_used) *cigar_used = used;
+  }
+  HIPOK(b, hipEventRecord(b->ev_used, hs));
+  rewrite_records(pr, g, ids, with_cigar, out);
+  return SW_OK;
+}
+
 // sw_align_hits, sw_align_set_hits and sw_align_strand_hits.
 sw_status host_call(sw_bank* b, const uint8_t* residues, size_t residues_len,
                     const uint64_t* offsets, const uint32_t* lens, const uint64_t* ids, size_t n,
@@ -426,51 +496,16 @@ sw_status host_call(sw_bank* b, const uint8_t* residues, size_t residues_len,
   hipStream_t hs = b->stream;
   SwkAlign p{};
   if ((st = stage_hits(b, pr, g, p, hs)) != SW_OK) return st;
-  // passes A and B, the records back
-  if ((st = timed_on(b, hs, [&] { return swk_launch_align_ends(&p, hs); })) != SW_OK) return st;
-  HIPOK(b, hipMemcpyAsync(out, b->al_out.p, n_hits * sizeof(sw_alignment), hipMemcpyDeviceToHost,
-                          hs));
-  HIPOK(b, hipStreamSynchronize(hs));
   size_t chunks = 0;
-  cigar_cap = std::min<size_t>(cigar_cap, 0xFFFFFFFFu);  // (cigar_offset is 32 bits)
-  const bool with_cigar = cigar && cigar_cap;
-  if (with_cigar) {
-    const Windows w = plan_windows(out, n_hits, dir_budget());
-    std::vector<uint32_t> ops;
-    if (!w.list.empty()) {  // passes C and D chunk by chunk, the records and the ops back
-      HIPOK(b, b->al_dirs.reserve((size_t)w.most));
-      HIPOK(b, b->al_cig.reserve((size_t)w.cig));
-      HIPOK(b, b->al_list.reserve(w.list.size()));
-      HIPOK(b, b->al_plan.reserve(w.plan.size()));
-      HIPOK(b, hipMemcpyAsync(b->al_list.p, w.list.data(), w.list.size() * 4,
-                              hipMemcpyHostToDevice, hs));
-      HIPOK(b, hipMemcpyAsync(b->al_plan.p, w.plan.data(), w.plan.size() * sizeof(SwkAlignPlan),
-                              hipMemcpyHostToDevice, hs));
-      p.cigar = b->al_cig.p;
-      p.cigar_stride = 1;  // (places come from the plan)
-      st = timed_on(b, hs, [&] {
-        for (size_t c = 0; c + 1 < w.cut.size(); ++c) {
-          if (w.cut[c + 1] == w.cut[c]) continue;
-          const hipError_t e =
-              swk_launch_align_paths(&p, b->al_list.p + w.cut[c], 0, w.cut[c + 1] - w.cut[c],
-                                     b->al_plan.p + w.cut[c], 0, b->al_dirs.p, hs);
-          if (e != hipSuccess) return e;
-          ++chunks;
-        }
-        return hipSuccess;
-      });
-      if (st != SW_OK) return st;
-      ops.resize((size_t)w.cig);
-      HIPOK(b, hipMemcpyAsync(out, b->al_out.p, n_hits * sizeof(sw_alignment),
-                              hipMemcpyDeviceToHost, hs));
-      HIPOK(b, hipMemcpyAsync(ops.data(), b->al_cig.p, ops.size() * 4, hipMemcpyDeviceToHost, hs));
-      HIPOK(b, hipStreamSynchronize(hs));
-    }
-    const size_t used = pack_ops(w, ops, out, n_hits, cigar, cigar_cap);
-    if (cigar_used) *cigar_used = used;
-  }
-  HIPOK(b, hipEventRecord(b->ev_used, hs));
-  rewrite_records(pr, g, ids, with_cigar, out);
+  st = host_passes(
+      b, pr, g, ids, hs, [&](hipStream_t s) { return swk_launch_align_ends(&p, s); },
+      [&](const uint32_t* list, size_t count, const SwkAlignPlan* plan, hipStream_t s) {
+        p.cigar = b->al_cig.p;
+        p.cigar_stride = 1;  // (places come from the plan)
+        return swk_launch_align_paths(&p, list, 0, count, plan, 0, b->al_dirs.p, s);
+      },
+      swk_align_dir_dwords, out, cigar, cigar_cap, cigar_used, chunks);
+  if (st != SW_OK) return st;
   name_kernel(b, pr.set, n_hits, chunks, pr.strand_call, pr.frame_call);
   return SW_OK;
 }
@@ -706,5 +741,178 @@ extern "C" sw_status sw_align_frame_hits(sw_bank* b, const uint8_t* residues, si
     out[h].id = ids ? ids[t] : t;
     frame_record(out[h], hf[h], lens[t]);
   }
+  return SW_OK;
+}
+
+// ---- alignments of frameshift hits -------------------------------------------
+// Hit h (query i, target k) is aligned over the three frames of the better strand of its DNA
+// target by the kernels of swbank_kfsalign.hip, which read the batch as it lies and write the
+// whole record (strand, frame, nucleotide coordinates) themselves; the pair list, the chunks of
+// the direction store and the host form's staging are the code above.
+namespace {
+
+// The launch block over a batch and a pair list already on the device.
+SwkFsAlign fshift_block(sw_bank* b, const uint8_t tab[64], int32_t frameshift,
+                        const uint8_t* d_res, const uint64_t* d_offs, const uint32_t* d_lens,
+                        const uint64_t* d_ids, size_t n, uint32_t max_len,
+                        const uint32_t* d_hit_queries, size_t hits_per_query,
+                        const uint64_t* d_hits, size_t n_hits, void* d_out) {
+  const size_t nq = query_count(b);
+  SwkFsAlign f{};
+  f.res = d_res;
+  f.offs = d_offs;
+  f.lens = d_lens;
+  f.ids = d_ids;
+  f.hits = d_hits;
+  f.n_hits = n_hits;
+  f.n = n;
+  f.max_len = max_len;
+  f.qtab = reinterpret_cast<const uint2*>(b->al_tab.p);
+  f.mat = reinterpret_cast<const int8_t*>(b->al_tab.p + nq * sizeof(uint2));
+  f.query = b->al_tab.p + nq * sizeof(uint2) + b->matrix.size();
+  f.nq = (uint32_t)nq;
+  f.qlen = (uint32_t)b->query.size();  // (a set: its longest query)
+  f.alpha = (uint32_t)b->alpha;
+  f.hit_queries = d_hit_queries;
+  f.hits_per_query = (uint32_t)hits_per_query;
+  std::memcpy(f.table, tab, 64);
+  f.o = b->gap_open + b->gap_extend;
+  f.e = b->gap_extend;
+  f.fs = frameshift;
+  f.out = d_out;
+  return f;
+}
+
+// The bank after the opening checks: prepare()d, the queries' table on the device.
+sw_status fshift_ready(sw_bank* b, const char* what) {
+  sw_status st = prepare(b);
+  if (st != SW_OK) return st;
+  if ((size_t)b->alpha * b->alpha != b->matrix.size() || b->alpha > SW_PROTEIN_ALPHA)
+    return fail(b, SW_ERR_UNSUPPORTED, "%s: alphabet %d too large", what, b->alpha);
+  return prepare_align(b);
+}
+
+// Pass A packs a lane's best cell as step << 4 | row: strands of less than 2^29 codes.
+constexpr uint32_t FSALIGN_MAX_LEN = (1u << 29) - 1;
+
+void name_fshift(sw_bank* b, size_t hits, size_t chunks) {
+  snprintf(b->last_kernel, sizeof(b->last_kernel), "align-fshift i32 nq=%zu hits=%zu chunks=%zu",
+           query_count(b), hits, chunks);
+}
+
+}  // namespace
+
+extern "C" sw_status sw_align_fshift_hits_device(sw_bank* b, const uint8_t* d_res,
+                                                 const uint64_t* d_offs, const uint32_t* d_lens,
+                                                 const uint64_t* d_ids, size_t n, uint32_t max_len,
+                                                 const uint8_t* codon_table, int32_t frameshift,
+                                                 const uint32_t* d_hit_queries,
+                                                 size_t hits_per_query, const uint64_t* d_hits,
+                                                 size_t n_hits, sw_alignment* d_out,
+                                                 uint32_t* d_cigar, uint32_t cigar_stride,
+                                                 void* stream) {
+  DevGuard dev_guard(b);  // on the bank's device; the caller's is restored on return (ABI 6)
+  if (!b) return SW_ERR_ARG;
+  uint8_t tab[64];
+  sw_status st = fshift_opening(b, "sw_align_fshift_hits_device", codon_table, frameshift, tab);
+  if (st != SW_OK) return st;
+  // a hand-off fault latched by an earlier device call is returned before anything runs
+  if (const sw_status fs = take_fault(b, 0); fs != SW_OK) return fs;
+  if (on_root(b, stream, st, [&](sw_bank* r, void* s) {
+        return sw_align_fshift_hits_device(r, d_res, d_offs, d_lens, d_ids, n, max_len,
+                                           codon_table, frameshift, d_hit_queries, hits_per_query,
+                                           d_hits, n_hits, d_out, d_cigar, cigar_stride, s);
+      }))
+    return st;
+  if ((st = fshift_ready(b, "sw_align_fshift_hits_device")) != SW_OK) return st;
+  if (n_hits == 0) return SW_OK;
+  if (!d_res || !d_offs || !d_lens || !d_out || n == 0)
+    return fail(b, SW_ERR_ARG, "null device buffer or an empty batch");
+  const Pairs pr{true, d_hit_queries, hits_per_query, d_hits, n_hits};
+  if ((st = check_pairs(b, pr, n)) != SW_OK) return st;
+  if (d_cigar && cigar_stride && (uint64_t)n_hits * cigar_stride > 0xFFFFFFFFull)
+    return fail(b, SW_ERR_ARG, "n_hits x cigar_stride must fit 32 bits (cigar_offset)");
+  if (max_len > FSALIGN_MAX_LEN)
+    return fail(b, SW_ERR_UNSUPPORTED, "sw_align_fshift_hits_device: max_len %u (at most %u)",
+                max_len, FSALIGN_MAX_LEN);
+  HIPOK(b, hipSetDevice(b->device));
+  hipStream_t hs = stream_or(b, stream);
+  SwkFsAlign f = fshift_block(b, tab, frameshift, d_res, d_offs, d_lens, d_ids, n, max_len,
+                              d_hit_queries, hits_per_query, d_hits, n_hits, d_out);
+  f.cigar = d_cigar;
+  f.cigar_stride = d_cigar ? cigar_stride : 0;
+  HIPOK(b, hipStreamWaitEvent(hs, b->ev_ready, 0));  // the queries' codes are uploaded
+  HIPOK(b, hipStreamWaitEvent(hs, b->ev_used, 0));   // bank scratch is free
+  st = timed_on(b, hs, [&] { return swk_launch_fsalign_ends(&f, hs); });
+  size_t chunks = 0;
+  if (st == SW_OK && f.cigar_stride) {
+    const uint64_t slot = swk_fsalign_dir_dwords(f.qlen, f.qlen, max_len >= 3 ? max_len - 2 : 0);
+    st = paths_in_slots(b, n_hits, slot, hs, chunks, [&](size_t h0, size_t count) {
+      return swk_launch_fsalign_paths(&f, nullptr, h0, count, nullptr, slot, b->al_dirs.p, hs);
+    });
+  }
+  // whatever was launched reads the table and the scratch: the next use is ordered after it
+  const hipError_t er = hipEventRecord(b->ev_used, hs);
+  if (st != SW_OK) return st;
+  HIPOK(b, er);
+  name_fshift(b, n_hits, chunks);
+  return SW_OK;
+}
+
+extern "C" sw_status sw_align_fshift_hits(sw_bank* b, const uint8_t* residues, size_t residues_len,
+                                          const uint64_t* offsets, const uint32_t* lens,
+                                          const uint64_t* ids, size_t n,
+                                          const uint8_t* codon_table, int32_t frameshift,
+                                          const uint32_t* hit_queries, size_t hits_per_query,
+                                          const uint64_t* hits, size_t n_hits, sw_alignment* out,
+                                          uint32_t* cigar, size_t cigar_cap, size_t* cigar_used) {
+  DevGuard dev_guard(b);  // on the bank's device; the caller's is restored on return (ABI 6)
+  if (!b) return SW_ERR_ARG;
+  if (cigar_used) *cigar_used = 0;
+  uint8_t tab[64];
+  sw_status st = fshift_opening(b, "sw_align_fshift_hits", codon_table, frameshift, tab);
+  if (st != SW_OK) return st;
+  if (on_root(b, nullptr, st, [&](sw_bank* r, void*) {  // (hit lists are small)
+        return sw_align_fshift_hits(r, residues, residues_len, offsets, lens, ids, n, codon_table,
+                                    frameshift, hit_queries, hits_per_query, hits, n_hits, out,
+                                    cigar, cigar_cap, cigar_used);
+      }))
+    return st;
+  if ((st = fshift_ready(b, "sw_align_fshift_hits")) != SW_OK) return st;
+  if (n_hits == 0) return SW_OK;
+  if (!offsets || !lens || !out) return fail(b, SW_ERR_ARG, "null host buffer");
+  const Pairs pr{true, hit_queries, hits_per_query, hits, n_hits};
+  if ((st = check_pairs(b, pr, n)) != SW_OK) return st;
+  Gathered g;
+  if ((st = gather_hits(b, residues, residues_len, offsets, lens, n, pr, g)) != SW_OK) return st;
+  for (size_t h = 0; h < n_hits; ++h)  // (the gathering knows the bank's protein alphabet)
+    for (uint32_t i = 0; i < g.lens[h]; ++i)
+      if (g.res[g.offs[h] + i] >= SW_DNA_ALPHA)
+        return fail(b, SW_ERR_ARG, "target %llu code %u at %u is no DNA code",
+                    (unsigned long long)target_of(pr, h), g.res[g.offs[h] + i], i);
+  if (g.max_len > FSALIGN_MAX_LEN)
+    return fail(b, SW_ERR_UNSUPPORTED, "sw_align_fshift_hits: a target of %u codes (at most %u)",
+                g.max_len, FSALIGN_MAX_LEN);
+  HIPOK(b, hipSetDevice(b->device));
+  hipStream_t hs = b->stream;
+  SwkAlign p{};  // (the staged buffers only: no launch block, no scratch rows)
+  if ((st = stage_hits(b, pr, g, p, hs, false)) != SW_OK) return st;
+  // hit h is target h of the gathered batch against query al_hq[h]
+  SwkFsAlign f = fshift_block(b, tab, frameshift, p.res, p.offs, p.lens, nullptr, n_hits,
+                              g.max_len, p.hit_queries, 0, nullptr, n_hits, p.out);
+  size_t chunks = 0;
+  st = host_passes(
+      b, pr, g, ids, hs, [&](hipStream_t s) { return swk_launch_fsalign_ends(&f, s); },
+      [&](const uint32_t* list, size_t count, const SwkAlignPlan* plan, hipStream_t s) {
+        f.cigar = b->al_cig.p;
+        f.cigar_stride = 1;  // (places come from the plan)
+        return swk_launch_fsalign_paths(&f, list, 0, count, plan, 0, b->al_dirs.p, s);
+      },
+      [&](uint32_t Q, uint32_t L) {  // (L nucleotides hold L - 2 codon starts)
+        return swk_fsalign_dir_dwords(f.qlen, Q, L >= 3 ? L - 2 : 0);
+      },
+      out, cigar, cigar_cap, cigar_used, chunks);
+  if (st != SW_OK) return st;
+  name_fshift(b, n_hits, chunks);
   return SW_OK;
 }

@@ -1009,6 +1009,10 @@ sw_status multi_resident(sw_bank* b, const sw_device_batch* per, int32_t* d_gath
                          hipStream_t hs);
 // ---- swbank_align.hip: the queries' codes and the matrix on the device (al_tab), after prepare()
 sw_status prepare_align(sw_bank* b);
+// ---- swbank_fshift.hip: what a frameshift entry checks first (bank, model, fs, table -> tab,
+// state, query length), in the header's order
+sw_status fshift_opening(sw_bank* b, const char* what, const uint8_t* codon_table,
+                         int32_t frameshift, uint8_t tab[64]);
 // ---- swbank_launch.hip (device batches against a query set; sstride: between query rows)
 sw_status launch_set(sw_bank* b, const uint8_t* d_res, const uint64_t* d_offs,
                      const uint32_t* d_lens, size_t n, uint32_t min_len, uint32_t max_len,

@@ -7,9 +7,8 @@
 // stages its batch and results in the frame search's host buffers (both calls synchronise).
 #include "swbank_bank.h"
 
-namespace {
-
-// What both forms check before anything else, in the order of the header's list.
+// What every frameshift entry (the alignments of swbank_align.hip too) checks before anything
+// else, in the order of the header's list.
 sw_status fshift_opening(sw_bank* b, const char* what, const uint8_t* codon_table,
                          int32_t frameshift, uint8_t tab[64]) {
   if (b->cfg.alphabet != SW_ALPHABET_PROTEIN)
@@ -29,8 +28,6 @@ sw_status fshift_opening(sw_bank* b, const char* what, const uint8_t* codon_tabl
                 b->query.size(), SW_FSHIFT_MAX_QUERY);
   return SW_OK;
 }
-
-}  // namespace
 
 extern "C" sw_status sw_score_fshift_device(sw_bank* b, const uint8_t* d_res,
                                             const uint64_t* d_offs, const uint32_t* d_lens,

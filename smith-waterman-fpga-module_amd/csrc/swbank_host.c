@@ -184,7 +184,8 @@ size_t sw_cigar_string(const uint32_t *ops, size_t n_ops, char *buf, size_t cap)
     const uint32_t code = ops[k] & 15u;
     const int w = snprintf(tmp, sizeof(tmp), "%u%c", (unsigned)(ops[k] >> 4),
                            code == SW_CIGAR_M ? 'M' : code == SW_CIGAR_I ? 'I'
-                           : code == SW_CIGAR_D ? 'D' : '?');
+                           : code == SW_CIGAR_D ? 'D' : code == SW_CIGAR_FS_SKIP ? '/'
+                           : code == SW_CIGAR_FS_BACK ? '\\' : '?');
     for (int c = 0; c < w; ++c, ++need)
       if (buf && need + 1 < cap) buf[need] = tmp[c];
   }

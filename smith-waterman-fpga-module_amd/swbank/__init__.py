@@ -57,6 +57,7 @@ EXPORTS = (
     "sw_translate_codes", "sw_translate_batch_device", "sw_score_frames",
     "sw_score_frames_device", "sw_align_frame_hits", "sw_align_frame_hits_device",
     "sw_score_fshift", "sw_score_fshift_device",
+    "sw_align_fshift_hits", "sw_align_fshift_hits_device",
 )
 ABI_VERSION = 6
 COUNTERS = ("stream_calls", "stream_reruns", "stream_declined", "chunked_calls", "device_sorts",
@@ -65,6 +66,8 @@ COUNTERS = ("stream_calls", "stream_reruns", "stream_declined", "chunked_calls",
             "h2d_bytes")
 MAX_DEVICES = 16
 CIGAR_M, CIGAR_I, CIGAR_D = 0, 1, 2          # BAM codes: I consumes query only, D target only
+CIGAR_FS_SKIP, CIGAR_FS_BACK = 3, 4          # frameshift hits: the next codon starts one base
+#                                              later ('/') or one base earlier ('\'), length 1
 ALIGN_EMPTY, ALIGN_NO_PATH = 1, 2            # sw_alignment.flags
 ALIGN_NO_HIT = 4                             # ... the slot named no pair (with ALIGN_EMPTY)
 ALIGN_REVERSE = 8                            # ... aligned against the target's reverse complement
@@ -291,6 +294,9 @@ def lib() -> ctypes.CDLL:
                                              P]),
         "sw_score_fshift": (i32, [P, P, sz, P, P, sz, P, i32, P, P]),
         "sw_score_fshift_device": (i32, [P, P, P, P, sz, u32, P, i32, P, P, P]),
+        "sw_align_fshift_hits": (i32, [P, P, sz, P, P, P, sz, P, i32, P, sz, P, sz, P, P, sz, P]),
+        "sw_align_fshift_hits_device": (i32, [P, P, P, P, P, sz, u32, P, i32, P, sz, P, sz, P, P,
+                                              u32, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -1042,6 +1048,57 @@ class ScoreBank:
         self._check(lib().sw_align_frame_hits_device(
             self._h, d_res or None, d_offs or None, d_lens or None, d_ids or None, n, max_len,
             _p(tab) if tab is not None else None, d_frames or None, d_hit_queries or None,
+            hits_per_query, d_hits or None, n_hits, d_out or None, d_cigar or None, cigar_stride,
+            stream or None))
+
+    # alignments of frameshift hits: where a hit of score_frameshift lies and where it shifts
+    def align_frameshift_hits(self, residues: np.ndarray, offsets: np.ndarray, lens: np.ndarray,
+                              frameshift: int, hits=None, hit_queries=None,
+                              hits_per_query: int = 0, ids: Optional[np.ndarray] = None,
+                              cigar_cap: Optional[int] = None, n_hits: Optional[int] = None,
+                              codon_table=None) -> list:
+        """sw_align_fshift_hits: the pair list of align_set_hits over a host DNA batch; the call
+        scores both strands itself.  Alignment.frame is the frame of the hit's first codon on its
+        strand, t_start / t_end are nucleotide positions on the forward target; the CIGAR is in
+        amino-acid columns with CIGAR_FS_SKIP ('/') and CIGAR_FS_BACK ('\\') ops of length 1 where
+        the next codon starts one base later or earlier than the frame says."""
+        res, offs, ln, idv = validate_batch(residues, offsets, lens, ids)
+        tab = _codon_table(codon_table)
+        hv = None if hits is None else np.ascontiguousarray(hits, dtype=np.uint64).reshape(-1)
+        hq = None if hit_queries is None else \
+            np.ascontiguousarray(hit_queries, dtype=np.uint32).reshape(-1)
+        if n_hits is None:
+            n_hits = len(hv) if hv is not None else len(hq) if hq is not None else len(ln)
+        if (hv is not None and len(hv) < n_hits) or (hq is not None and len(hq) < n_hits):
+            raise ValueError("hits / hit_queries shorter than n_hits")
+        out = np.zeros(max(n_hits, 1), dtype=ALIGNMENT_DTYPE)
+        if cigar_cap is None:  # m M runs between shifts and I runs span at least 2 m + 1 bases
+            tv = hv[:n_hits] if hv is not None else np.arange(min(n_hits, len(ln)), dtype=np.uint64)
+            sel = tv[tv < len(ln)].astype(np.int64)
+            cigar_cap = 2 * int(ln[sel].astype(np.int64).sum()) + n_hits
+        cig = np.zeros(max(cigar_cap, 1), dtype=np.uint32)
+        used = ctypes.c_size_t()
+        self._check(lib().sw_align_fshift_hits(
+            self._h, _p(res), res.size, _p(offs), _p(ln), _p(idv) if idv is not None else None,
+            len(ln), _p(tab) if tab is not None else None, frameshift,
+            _p(hq) if hq is not None else None, hits_per_query,
+            _p(hv) if hv is not None else None, n_hits, _p(out),
+            _p(cig) if cigar_cap else None, cigar_cap, ctypes.byref(used)))
+        return alignments_from(out[:n_hits], cig)
+
+    def align_frameshift_hits_device(self, d_res: int, d_offs: int, d_lens: int, n: int,
+                                     max_len: int, frameshift: int, n_hits: int, d_out: int,
+                                     d_hits: int = 0, d_hit_queries: int = 0,
+                                     hits_per_query: int = 0, d_cigar: int = 0,
+                                     cigar_stride: int = 0, stream: int = 0, d_ids: int = 0,
+                                     codon_table=None):
+        """sw_align_fshift_hits_device: device pointers (ints), the pair list of
+        align_set_hits_device over the DNA batch score_frameshift_device scored.  Async on
+        `stream` (0: the bank's own stream; sync() before reading)."""
+        tab = _codon_table(codon_table)
+        self._check(lib().sw_align_fshift_hits_device(
+            self._h, d_res or None, d_offs or None, d_lens or None, d_ids or None, n, max_len,
+            _p(tab) if tab is not None else None, frameshift, d_hit_queries or None,
             hits_per_query, d_hits or None, n_hits, d_out or None, d_cigar or None, cigar_stride,
             stream or None))
 
