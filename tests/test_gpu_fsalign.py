@@ -4,8 +4,8 @@ ops, with the C model of tests/fsalign_cases.py (itself checked against the plai
 restatement with its brute-force start by tests/test_fsalign_cases.py), through the host form's
 plan and through the device form's slots, plain and with poisoned buffers: the kernels' three row
 counts, each pass at its own lane and block seams, the targets' edges, both tables, an asymmetric matrix, a query set in both pair layouts,
-the budget and the CIGAR space, one long target, the chain from the score call, the six-frame
-anchor, the refusals.  The CPU references are computed once per process and shared."""
+the budget and the CIGAR space, one long target, the chain from the score call, every record's
+score and strand against the score call's, the six-frame anchor, the refusals.  The CPU references are computed once per process and shared."""
 import numpy as np
 import pytest
 
@@ -479,6 +479,31 @@ def test_chain_from_the_score_call_on_one_stream(poison, monkeypatch):
     for a, (i, t) in zip(got, pairs):
         assert a.score == sc[i][t] == wsc[0][i][t] and a.reverse == bool(sd[i][t]) and a.has_path
     _check(got, _want(qs, seqs, pairs, O.BLOSUM62, F.PEN, -15), pairs, "chain")
+
+
+@pytest.mark.parametrize("fs", [-15, -32767])
+@pytest.mark.parametrize("m", [5, 257, 513])
+def test_record_scores_are_the_score_calls_on_every_target(m, fs):
+    """One query per row count of the kernels against the 64 seam targets, every target a hit with
+    no selection in between, so ties between the strands and zero scores are among them: the
+    record's score is score_frameshift_device's, its strand flag that call's strand, and a target
+    that scores 0 comes back SW_ALIGN_EMPTY.  (The two calls run the same walk; this holds them
+    to it.)"""
+    q, seqs, _ = TG._seam_case(m)
+    assert len(seqs) == 64 and max(len(t) for t in seqs) <= 260
+    bt = TG._cached(("seam-batch", m), lambda: TG.Batch(seqs))
+    pairs = [(0, k) for k in range(bt.n)]
+    with TG._bank() as bank:
+        bank.load_query(q)
+        sc, sd, _ = TG._score_device(bank, bt, 1, fs)
+        got = _device(bank, bt, pairs, fs, 0, cigar=False)
+    assert (sc[0] > 0).sum() >= 32 and sc[0][5] == sc[0][9] == 0  # (5 and 9 hold no codon)
+    for k, a in enumerate(got):
+        assert a.index == k and a.score == sc[0][k], (m, fs, k, a.score, sc[0][k])
+        if sc[0][k] > 0:
+            assert a.reverse == bool(sd[0][k]) and not a.empty, (m, fs, k, a.flags, sd[0][k])
+        else:
+            assert a.flags == S.ALIGN_EMPTY, (m, fs, k, a.flags)
 
 
 @pytest.mark.parametrize("poison", ["plain", "poison"])
