@@ -94,7 +94,8 @@ extern "C" {
  *        sw_score_frames[_device], sw_align_frame_hits[_device], SW_ALIGN_FRAME_SHIFT / _MASK;
  *        (test SWBANK_HAS_FSHIFT) the frameshift-tolerant translated search --
  *        sw_score_fshift[_device], SW_FSHIFT_MAX_QUERY; (test SWBANK_HAS_FSHIFT_ALIGN) alignments
- *        of frameshift hits -- sw_align_fshift_hits[_device], SW_CIGAR_FS_SKIP / _BACK. */
+ *        of frameshift hits -- sw_align_fshift_hits[_device], SW_CIGAR_FS_SKIP / _BACK; (test
+ *        SWBANK_HAS_FSHIFT_STATS) their statistics -- sw_estimate_fshift_statistics[_device]. */
 #define SWBANK_ABI_VERSION 6
 #define SWBANK_HAS_ALIGN 1
 #define SWBANK_HAS_TOPK 1
@@ -886,7 +887,7 @@ sw_status sw_align_frame_hits(sw_bank *bank, const uint8_t *residues, size_t res
  * (SW_GAP_MERGED: SW_ERR_UNSUPPORTED); 0 >= frameshift >= -32767 (else SW_ERR_ARG); every query
  * of the loaded set has at most SW_FSHIFT_MAX_QUERY rows (else SW_ERR_UNSUPPORTED).  Scores are
  * exact int32 with no width limit.  Alignments of shifted hits: sw_align_fshift_hits[_device]
- * below; statistics of shifted hits do not exist. */
+ * below; their statistics: sw_estimate_fshift_statistics[_device] after those. */
 #define SWBANK_HAS_FSHIFT 1
 #define SW_FSHIFT_MAX_QUERY 1024
 
@@ -990,6 +991,56 @@ sw_status sw_align_fshift_hits(sw_bank *bank, const uint8_t *residues, size_t re
                                const uint32_t *hit_queries, size_t hits_per_query,
                                const uint64_t *hits, size_t n_hits, sw_alignment *out,
                                uint32_t *cigar, size_t cigar_cap, size_t *cigar_used);
+
+/* ---- statistics of frameshift hits (ABI 6 addition) ----------------------------------------------
+ * Lambda and K of the frameshift-tolerant search, estimated like those of the plain search ("hit
+ * significance" above) but with this search's own score: three frames in one matrix and two
+ * strands give chance more places to score, so a fit made on a forward protein search would
+ * understate E.
+ *
+ * Definition.  For every round r < rounds (rounds >= 1):
+ *   - target k of the DNA batch is shuffled under seed + r exactly as sw_shuffle_batch_device
+ *     defines it: the bases are shuffled, N included, keyed by the batch position k;
+ *   - every loaded query is scored against every shuffled target with the search score of
+ *     sw_score_fshift (the larger of the two strand scores) under `codon_table` and `frameshift`;
+ *   - the scores go into one histogram row per query exactly as sw_score_histogram_device counts
+ *     them, the lengths being the targets' lengths in NUCLEOTIDES; targets of length 0 are skipped.
+ * After the last round row i is fitted by sw_fit_statistics with query_len = the residues of query
+ * i, into out[0 .. sw_query_count()), host memory.  n_samples, n_clamped, SW_STAT_CLAMPED and
+ * SW_STAT_DEGENERATE are as for sw_estimate_statistics.
+ *
+ * Significance of a hit: sw_hit_significance[_device] unchanged, with d_lens / target_lens in
+ * nucleotides (the batch's own lengths, as sw_top_hits_device indexes them) and db_size the number
+ * of library sequences.  Both strands are already inside the score, as they are inside the
+ * shuffled scores the fit was made on: db_size is not doubled.
+ *
+ * The work is enqueued on `stream` (NULL = the bank's) and the call returns after synchronising
+ * it.  The scratch (shuffled bases at a stride of max_len and nq x n scores) is bounded by
+ * SWBANK_STAT_MB as for sw_estimate_statistics_device, and slices cannot change a count.  Limits
+ * and refusals are sw_score_fshift's, in its order: protein banks, the Gotoh model, the frameshift
+ * range, the codon table, the state, queries of at most SW_FSHIFT_MAX_QUERY rows; then
+ * SW_ERR_ARG for a NULL buffer or out, n == 0, n >= 2^32, rounds == 0.  A latched hand-off fault
+ * is returned as elsewhere; a multi-device bank runs the call on its root.  No best hit is
+ * tracked.  sw_last_kernel reports "fshift-stats rounds=<r> nq=<nq> n=<n> slices=<s>"; with
+ * sw_bank_set_timing every shuffle, scoring and histogram pass of a slice is bracketed as one
+ * launch each (3 x rounds x slices in all). */
+#define SWBANK_HAS_FSHIFT_STATS 1
+
+/* Device buffers: the batch as for sw_score_fshift_device (every d_lens[k] <= max_len). */
+sw_status sw_estimate_fshift_statistics_device(sw_bank *bank, const uint8_t *d_residues,
+                                               const uint64_t *d_offsets, const uint32_t *d_lens,
+                                               size_t n, uint32_t max_len,
+                                               const uint8_t *codon_table, int32_t frameshift,
+                                               uint64_t seed, uint32_t rounds, sw_statistics *out,
+                                               void *stream);
+
+/* Host buffers, blocking; the batch as for sw_score_fshift (a target outside the residues or a
+ * code of 5 or more is SW_ERR_ARG): uploads it once and calls the device form. */
+sw_status sw_estimate_fshift_statistics(sw_bank *bank, const uint8_t *residues,
+                                        size_t residues_len, const uint64_t *offsets,
+                                        const uint32_t *lens, size_t n, const uint8_t *codon_table,
+                                        int32_t frameshift, uint64_t seed, uint32_t rounds,
+                                        sw_statistics *out);
 
 /* ---- profiling(≙ the CAPI AFU's cycle counters, capi_sample_aligner/hdl-verliog/afu.v
  *      _DEBUGGING_ "calculation #N completed, runtime: C cycles") ------------------------- */

@@ -129,6 +129,7 @@ extern "C" hipError_t swk_shuffle_batch(const uint8_t* in, const uint64_t* offs,
                                         const uint32_t* lens, size_t n, uint32_t max_len,
                                         uint64_t k0, uint64_t seed, uint8_t* out,
                                         uint64_t* out_offs, uint32_t stride, hipStream_t st);
+extern "C" uint32_t swk_shuffle_class_limit(int i);  // i < 0: the lane row; 0 past the last class
 extern "C" hipError_t swk_stat_hist(const int32_t* scores, const uint32_t* lens, size_t n,
                                     size_t nq, unsigned long long* counts,
                                     unsigned long long* len_sums, unsigned long long* clamped,

@@ -58,6 +58,7 @@ EXPORTS = (
     "sw_score_frames_device", "sw_align_frame_hits", "sw_align_frame_hits_device",
     "sw_score_fshift", "sw_score_fshift_device",
     "sw_align_fshift_hits", "sw_align_fshift_hits_device",
+    "sw_estimate_fshift_statistics", "sw_estimate_fshift_statistics_device",
 )
 ABI_VERSION = 6
 COUNTERS = ("stream_calls", "stream_reruns", "stream_declined", "chunked_calls", "device_sorts",
@@ -297,6 +298,9 @@ def lib() -> ctypes.CDLL:
         "sw_align_fshift_hits": (i32, [P, P, sz, P, P, P, sz, P, i32, P, sz, P, sz, P, P, sz, P]),
         "sw_align_fshift_hits_device": (i32, [P, P, P, P, P, sz, u32, P, i32, P, sz, P, sz, P, P,
                                               u32, P]),
+        "sw_estimate_fshift_statistics": (i32, [P, P, sz, P, P, sz, P, i32, u64, u32, P]),
+        "sw_estimate_fshift_statistics_device": (i32, [P, P, P, P, sz, u32, P, i32, u64, u32, P,
+                                                       P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -998,6 +1002,35 @@ class ScoreBank:
         scores = sc[:nq * n].reshape(nq, n)
         strands = sd[:nq * n].reshape(nq, n)
         return (scores[0], strands[0]) if nq == 1 else (scores, strands)
+
+    def estimate_frameshift_statistics_device(self, d_dna: int, d_offs: int, d_lens: int, n: int,
+                                              max_len: int, frameshift: int, seed: int = 0,
+                                              rounds: int = 1, codon_table=None,
+                                              stream: int = 0) -> list:
+        """sw_estimate_fshift_statistics_device: one Statistics per loaded query from `rounds`
+        shuffles of the device DNA batch (seeds seed .. seed + rounds - 1), each scored as
+        score_frameshift_device scores it.  Returns after synchronising.  hit_significance with
+        the targets' lengths in nucleotides gives the bits and E-values of frameshift hits."""
+        tab = _codon_table(codon_table)
+        out = (Statistics * max(self.query_count(), 1))()
+        self._check(lib().sw_estimate_fshift_statistics_device(
+            self._h, d_dna or None, d_offs or None, d_lens or None, n, max_len,
+            _p(tab) if tab is not None else None, frameshift, seed, rounds, out, stream or None))
+        return list(out)[:self.query_count()]
+
+    def estimate_frameshift_statistics(self, targets, frameshift: int, seed: int = 0,
+                                       rounds: int = 1, codon_table=None) -> list:
+        """sw_estimate_fshift_statistics: the same for host DNA targets (uploaded once), a
+        sequence of DNA code arrays or a packed batch as the tuple (residues, offsets, lens)."""
+        if not (isinstance(targets, tuple) and len(targets) == 3):
+            targets = pack_targets([np.asarray(t, np.uint8) for t in targets])
+        res, offs, ln, _ = validate_batch(*targets)
+        tab = _codon_table(codon_table)
+        out = (Statistics * max(self.query_count(), 1))()
+        self._check(lib().sw_estimate_fshift_statistics(
+            self._h, _p(res), res.size, _p(offs), _p(ln), len(ln),
+            _p(tab) if tab is not None else None, frameshift, seed, rounds, out))
+        return list(out)[:self.query_count()]
 
     def align_frame_hits(self, residues: np.ndarray, offsets: np.ndarray, lens: np.ndarray,
                          frames, hits=None, hit_queries=None, hits_per_query: int = 0,
