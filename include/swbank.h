@@ -886,8 +886,17 @@ sw_status sw_align_frame_hits(sw_bank *bank, const uint8_t *residues, size_t res
  * Limits: protein banks only (a DNA bank: SW_ERR_UNSUPPORTED); the Gotoh gap model only
  * (SW_GAP_MERGED: SW_ERR_UNSUPPORTED); 0 >= frameshift >= -32767 (else SW_ERR_ARG); every query
  * of the loaded set has at most SW_FSHIFT_MAX_QUERY rows (else SW_ERR_UNSUPPORTED).  Scores are
- * exact int32 with no width limit.  Alignments of shifted hits: sw_align_fshift_hits[_device]
- * below; their statistics: sw_estimate_fshift_statistics[_device] after those. */
+ * exact int32 with no width limit.  The bank's two scoring limits hold all the same, although
+ * the int32 kernel has neither: a matrix with max(0, largest entry) - smallest entry > 254, or
+ * Gotoh penalties with |gap_open| + |gap_extend| + max(0, largest entry) > 65535, is refused with
+ * SW_ERR_RANGE by sw_score_fshift[_device], sw_align_fshift_hits[_device] and
+ * sw_estimate_fshift_statistics[_device] alike (each prepares the bank's query tables, which are
+ * built for the 16-bit kernels), after the checks above and each call's argument checks and
+ * before any output is written; the bank stays usable.  Everything else of 0 >= gap_open,
+ * gap_extend >= -32767 and of int8 matrices is accepted: zero penalties, matrices without a
+ * positive entry (every score 0), entries of -128.  Alignments of shifted hits:
+ * sw_align_fshift_hits[_device] below; their statistics: sw_estimate_fshift_statistics[_device]
+ * after those. */
 #define SWBANK_HAS_FSHIFT 1
 #define SW_FSHIFT_MAX_QUERY 1024
 

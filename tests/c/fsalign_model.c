@@ -16,14 +16,17 @@ static int64_t max2(int64_t a, int64_t b) { return a > b ? a : b; }
 /* The best cell of the local matrix of rows q[m] against the amino acids a[P] of the codon starts
  * 0 .. P - 1: the highest H, then the smallest p, then the smallest i.  A mutant (the tests'
  * liveness check, mrow / mcol >= 0) loses the gap state at a seam: F does not extend into row
- * mrow, E does not extend into the columns of codon index mcol. */
+ * mrow, E does not extend into the columns of codon index mcol.  cells (optional): how many
+ * cells hold the best H. */
 static int64_t local_best(const uint8_t *q, size_t m, const uint8_t *a, size_t P,
                           const int8_t *sub, int alpha, int64_t o, int64_t e, int64_t fs,
-                          ptrdiff_t mrow, ptrdiff_t mcol, size_t *bi, size_t *bp) {
+                          ptrdiff_t mrow, ptrdiff_t mcol, size_t *bi, size_t *bp,
+                          size_t *cells) {
   int64_t *Hp = calloc(P + 4, sizeof *Hp), *Hc = calloc(P + 4, sizeof *Hc);
   int64_t *Fp = malloc((P + 4) * sizeof *Fp), *Fc = malloc((P + 4) * sizeof *Fc);
   int64_t *E = malloc((P + 4) * sizeof *E);
   int64_t best = 0;
+  size_t n_best = 0;
   *bi = *bp = 0;
   for (size_t p = 0; p < P + 4; ++p) Fp[p] = NEG;
   for (size_t i = 0; i < m; ++i) {
@@ -39,6 +42,7 @@ static int64_t local_best(const uint8_t *q, size_t m, const uint8_t *a, size_t P
       E[x] = max2(Hc[x - 3] + o, ((ptrdiff_t)(p / 3) == mcol ? NEG : E[x - 3]) + e);
       Fc[x] = max2(Hp[x] + o, ((ptrdiff_t)i == mrow ? NEG : Fp[x]) + e);
       Hc[x] = max2(max2(0, M), max2(E[x], Fc[x]));
+      n_best = Hc[x] > best ? 1 : n_best + (Hc[x] == best && best > 0);
       if (Hc[x] > best || (Hc[x] == best && best > 0 && (p < *bp || (p == *bp && i < *bi)))) {
         best = Hc[x];
         *bi = i;
@@ -57,6 +61,7 @@ static int64_t local_best(const uint8_t *q, size_t m, const uint8_t *a, size_t P
   free(Fp);
   free(Fc);
   free(E);
+  if (cells) *cells = n_best;
   return best;
 }
 
@@ -94,7 +99,7 @@ int64_t fsalign_mutant(const uint8_t *q, size_t m, const uint8_t *t, size_t L, c
   int64_t sc[2];
   for (int s = 0; s < 2; ++s) {
     translate(c[s], L, table, a[s]);
-    sc[s] = local_best(q, m, a[s], P, sub, alpha, o, e, fs, ar, ac, &ei[s], &ep[s]);
+    sc[s] = local_best(q, m, a[s], P, sub, alpha, o, e, fs, ar, ac, &ei[s], &ep[s], NULL);
   }
   const int rev = sc[1] > sc[0];
   const int64_t score = sc[rev];
@@ -107,7 +112,7 @@ int64_t fsalign_mutant(const uint8_t *q, size_t m, const uint8_t *t, size_t L, c
     for (size_t p = 0; p <= p_end; ++p) ra[p] = a[rev][p_end - p];
     size_t si, sp;
     const int64_t back =
-        local_best(rq, q_end + 1, ra, p_end + 1, sub, alpha, o, e, fs, br, bc, &si, &sp);
+        local_best(rq, q_end + 1, ra, p_end + 1, sub, alpha, o, e, fs, br, bc, &si, &sp, NULL);
     free(rq);
     free(ra);
     if (back != score && !mpass) abort(); /* the reversal argument failed */
@@ -227,4 +232,28 @@ int64_t fsalign_model(const uint8_t *q, size_t m, const uint8_t *t, size_t L, co
                       int32_t fshift, uint32_t *rec, uint32_t *ops, size_t ops_cap) {
   return fsalign_mutant(q, m, t, L, sub, alpha, table, gap_open, gap_extend, fshift, rec, ops,
                         ops_cap, 0, -1, -1);
+}
+
+/* How many cells of the winning strand's local matrix hold the score (0 when nothing scores):
+ * more than one means the tie rule decided where the hit ends. */
+size_t fsalign_best_cells(const uint8_t *q, size_t m, const uint8_t *t, size_t L,
+                          const int8_t *sub, int alpha, const uint8_t *table, int32_t gap_open,
+                          int32_t gap_extend, int32_t fshift) {
+  if (L < 3 || m == 0) return 0;
+  const size_t P = L - 2;
+  uint8_t *c = malloc(L), *a = malloc(P);
+  int64_t sc[2];
+  size_t cells[2], bi, bp;
+  for (int s = 0; s < 2; ++s) {
+    for (size_t i = 0; i < L; ++i) {
+      const uint8_t v = t[L - 1 - i];
+      c[i] = s ? (v < 4 ? (uint8_t)(v ^ 2) : v) : t[i];
+    }
+    translate(c, L, table, a);
+    sc[s] = local_best(q, m, a, P, sub, alpha, (int64_t)gap_open + gap_extend, gap_extend, fshift,
+                       -1, -1, &bi, &bp, &cells[s]);
+  }
+  free(c);
+  free(a);
+  return cells[sc[1] > sc[0]];
 }
