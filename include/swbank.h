@@ -95,7 +95,9 @@ extern "C" {
  *        (test SWBANK_HAS_FSHIFT) the frameshift-tolerant translated search --
  *        sw_score_fshift[_device], SW_FSHIFT_MAX_QUERY; (test SWBANK_HAS_FSHIFT_ALIGN) alignments
  *        of frameshift hits -- sw_align_fshift_hits[_device], SW_CIGAR_FS_SKIP / _BACK; (test
- *        SWBANK_HAS_FSHIFT_STATS) their statistics -- sw_estimate_fshift_statistics[_device]. */
+ *        SWBANK_HAS_FSHIFT_STATS) their statistics -- sw_estimate_fshift_statistics[_device];
+ *        (test SWBANK_HAS_GLOCAL) the global-local search -- sw_score_glocal[_device],
+ *        SW_ENDS_QUERY / _TARGET / _BOTH, SW_END_NONE, SW_GLOCAL_MAX_QUERY. */
 #define SWBANK_ABI_VERSION 6
 #define SWBANK_HAS_ALIGN 1
 #define SWBANK_HAS_TOPK 1
@@ -1050,6 +1052,78 @@ sw_status sw_estimate_fshift_statistics(sw_bank *bank, const uint8_t *residues,
                                         const uint32_t *lens, size_t n, const uint8_t *codon_table,
                                         int32_t frameshift, uint64_t seed, uint32_t rounds,
                                         sw_statistics *out);
+
+/* ---- global-local search: a query or a target scored end to end (ABI 6 addition) ---------------
+ * Every other score of this library is local: the best piece of the query against the best piece
+ * of the target, floored at 0.  The calls below score the whole query (what the FASTA suite's
+ * glsearch36 does), the whole target (reads as the batch against a set of references) or both
+ * (ggsearch36) with penalised boundaries, no floor and negative scores.  The definition is this
+ * library's own; nothing in the project this one was modelled on pins it.
+ *
+ * Definition: rows i = 0 .. m - 1 over the query q, columns j = 0 .. L - 1 over the strand t
+ * walked, o = gap_open + gap_extend and e = gap_extend (the bank's Gotoh penalties), no floor:
+ *     M(i,j) = s(q_i, t_j) + H(i-1, j-1)
+ *     E(i,j) = max(H(i, j-1) + o, E(i, j-1) + e)      a target residue against a gap
+ *     F(i,j) = max(H(i-1, j) + o, F(i-1, j) + e)      a query residue against a gap
+ *     H(i,j) = max(M, E, F)
+ * H(-1,-1) = 0; E and F are -infinity outside the matrix.  `ends` selects the boundaries and the
+ * result:
+ *     ends                 H(i,-1), i >= 0   H(-1,j), j >= 0   score                        end position
+ *     SW_ENDS_QUERY  (1)   o + i e           0                 max over j = -1 .. L-1 of    that j, the smallest
+ *                                                              H(m-1, j)                    on a tie
+ *     SW_ENDS_TARGET (2)   0                 o + j e           max over i = -1 .. m-1 of    that i, the smallest
+ *                                                              H(i, L-1)                    on a tie
+ *     SW_ENDS_BOTH   (3)   o + i e           o + j e           H(m-1, L-1)                  SW_END_NONE
+ * QUERY: the query end to end, the target local.  TARGET: the target end to end, the query local.
+ * The boundary index -1 is reported as SW_END_NONE: it is what L = 0 gives, or a query (a target)
+ * that is all gap.  With both_strands the reverse strand is rc(target), rc as sw_revcomp_codes;
+ * the search score is the larger strand score, the strand is 0 unless the reverse strand is
+ * strictly better, and a QUERY end position on the reverse strand is reported on the forward
+ * target, as L - 1 - j (a TARGET end position is a query row on either strand).
+ *
+ * Limits and refusals, checked in this order before anything else: both_strands on a protein bank
+ * is SW_ERR_UNSUPPORTED (DNA and protein banks are both accepted otherwise); SW_GAP_MERGED is
+ * SW_ERR_UNSUPPORTED; ends outside 1 .. 3 is SW_ERR_ARG; SW_ERR_STATE without penalties or a
+ * query; every query of the loaded set has at most SW_GLOCAL_MAX_QUERY rows, else
+ * SW_ERR_UNSUPPORTED.  Then each call's argument checks (n == 0 is SW_OK; a NULL buffer (n > 0) or
+ * n >= 2^32 is SW_ERR_ARG).  Then SW_ERR_RANGE, before any output is written and with the bank
+ * left usable: the bank's two scoring limits (see sw_score_fshift: the call prepares the bank's
+ * query tables), and one rule of its own,
+ *     |o| + (1024 + 64 + max_len) x max(|e|, 128) < 2^30
+ * with the caller's max_len (the host form: the longest listed target).  Every real cell lies at
+ * or above -(|o| + (m + L) x max(|e|, |smallest entry|)); the rule leaves room for the kernel's pad
+ * rows.  Scores are exact int32 and may be negative: sw_top_hits_device and
+ * sw_best_queries_device take them unchanged (mind min_score). */
+#define SWBANK_HAS_GLOCAL 1
+#define SW_GLOCAL_MAX_QUERY 1024
+#define SW_END_NONE UINT32_MAX
+enum { SW_ENDS_QUERY = 1, SW_ENDS_TARGET = 2, SW_ENDS_BOTH = 3 };
+
+/* Device buffers, asynchronous on `stream` (NULL = the bank's): the batch as for
+ * sw_score_batch_device (targets at any byte offset, d_lens[k] may be 0, every d_lens[k] <=
+ * max_len: codes of a target past max_len are not read).  Nothing is validated: a code past the
+ * bank's alphabet reads as the alphabet's last code -- N on a DNA bank, * (code 23) on a protein
+ * bank, the one code every protein matrix scores like an unknown residue.  With nq =
+ * sw_query_count(): d_scores receives the nq x n int32 scores, query-major; d_end_pos (may be
+ * NULL) the nq x n uint32 end positions; d_strands (may be NULL) the nq x n uint8 strands, all 0
+ * without both_strands.  One kernel reads the targets as they lie; the call owns no scratch.  No
+ * best hit is tracked.  A latched hand-off fault of an earlier device call is returned as by the
+ * other device calls; a multi-device bank runs the call on its root; sw_bank_sync covers it.
+ * sw_last_kernel reports "glocal ends=<e> nq=<nq> n=<n>"; with sw_bank_set_timing the call is
+ * bracketed as one launch. */
+sw_status sw_score_glocal_device(sw_bank *bank, const uint8_t *d_residues,
+                                 const uint64_t *d_offsets, const uint32_t *d_lens, size_t n,
+                                 uint32_t max_len, int32_t ends, int32_t both_strands,
+                                 int32_t *d_scores, uint32_t *d_end_pos, uint8_t *d_strands,
+                                 void *stream);
+
+/* Host buffers, blocking; the batch as for sw_score_batch (a target outside the residues or a
+ * code outside the bank's alphabet is SW_ERR_ARG): uploads it once and calls the device form.
+ * scores_out: nq x n; end_pos_out and strands_out: nq x n, each may be NULL. */
+sw_status sw_score_glocal(sw_bank *bank, const uint8_t *residues, size_t residues_len,
+                          const uint64_t *offsets, const uint32_t *lens, size_t n, int32_t ends,
+                          int32_t both_strands, int32_t *scores_out, uint32_t *end_pos_out,
+                          uint8_t *strands_out);
 
 /* ---- profiling(≙ the CAPI AFU's cycle counters, capi_sample_aligner/hdl-verliog/afu.v
  *      _DEBUGGING_ "calculation #N completed, runtime: C cycles") ------------------------- */

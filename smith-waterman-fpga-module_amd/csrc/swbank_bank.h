@@ -178,6 +178,17 @@ extern "C" hipError_t swk_fshift_score(const uint8_t* res, const uint64_t* offs,
                                        size_t nq, uint32_t qlen, uint32_t alpha,
                                        const uint8_t* table, int32_t o, int32_t e, int32_t fs,
                                        int32_t* scores, uint8_t* strands, hipStream_t st);
+// swbank_kglocal.hip: the score kernel of the global-local search (qtab / mat / query: al_tab's
+// parts; qlen: the longest query, at most SW_GLOCAL_MAX_QUERY; o = open + extend, e <= 0; ends:
+// SW_ENDS_*; both: the reverse strand too (DNA codes); scores, ends_out and strands (both
+// optional) nq x n) and the rows a lane holds for that qlen
+extern "C" int swk_glocal_rows(uint32_t qlen);
+extern "C" hipError_t swk_glocal_score(const uint8_t* res, const uint64_t* offs,
+                                       const uint32_t* lens, size_t n, uint32_t max_len,
+                                       const uint2* qtab, const int8_t* mat, const uint8_t* query,
+                                       size_t nq, uint32_t qlen, uint32_t alpha, int32_t o,
+                                       int32_t e, int32_t ends, int32_t both, int32_t* scores,
+                                       uint32_t* ends_out, uint8_t* strands, hipStream_t st);
 extern "C" hipError_t swk_stat_signif(const double* par, const int32_t* hit_scores,
                                       const uint64_t* hits, const uint32_t* lens, size_t k,
                                       size_t nq, double db_size, double* bits, double* evalues,
@@ -579,6 +590,9 @@ struct sw_bank {
   DevBuf<uint8_t> fr_hfr;
   DevBuf<int32_t> fr_hsc;
   hipEvent_t ev_frame = nullptr;
+  // the global-local search (swbank_glocal.hip): the host form's end positions on the device,
+  // beside fr_host / fr_hsc / fr_hfr and under ev_frame like them
+  DevBuf<uint32_t> gl_hend;
   using Seg = qtab::Seg;  // rows = W*R (last may be shorter); word offsets in qtab and qtab16
   std::vector<Seg> segs;
   qtab::Plan plan;  // prepare()'s analysis: what the set's and the int32 tables are built from

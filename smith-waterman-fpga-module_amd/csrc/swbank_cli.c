@@ -60,6 +60,14 @@
  *       it, as with -B.  The call knows the Gotoh gap model only, so -F implies -g.  Alignments
  *       and statistics of shifted hits do not exist yet: not with -A, -E or -S; and not with -B
  *       (both strands are searched already).
+ *   -G  q, t or b: the global-local search (sw_score_glocal; this library's own definition,
+ *       include/swbank.h): the query end to end against a piece of each record (q, what the FASTA
+ *       suite's glsearch36 scores), each record end to end against a piece of the query (t), or
+ *       both end to end (b, ggsearch36).  No floor: scores may be negative.  The call knows the
+ *       Gotoh gap model only, so -G implies -g.  With -B both strands are searched and " [f]" or
+ *       " [r]" follows every score, as above.  Alignments and statistics of global-local hits do
+ *       not exist yet: not with -A, -E or -S; and not with -X or -F (the translated searches are
+ *       local).
  *   -b  also print the bank's best hit ("best: >name score: S", ≙ max / vld_max) to stderr
  * FASTA: '>' starts a record (name = first token); sequence lines are concatenated; CR/LF,
  * blank lines and lower case are accepted; bytes outside the alphabet encode to N (DNA) or X
@@ -148,10 +156,12 @@ static void usage(const char *argv0) {
   fprintf(stderr,
           "usage: %s -q query.fa -l library.fa [-p match,mismatch,open,extend] [-P] [-g]\n"
           "          [-d device[,device...]] [-o out.txt] [-T] [-R scores.txt] [-b] [-A k]\n"
-          "          [-E rounds[,seed]] [-S lambda,K] [-B] [-X [-F frameshift]]\n"
+          "          [-E rounds[,seed]] [-S lambda,K] [-B] [-X [-F frameshift]] [-G q|t|b]\n"
           "  -X: protein query against a DNA library in six reading frames; not with -B\n"
           "  -F: with -X, follow hits across frameshifts at this penalty (0 .. -32767; implies -g);\n"
-          "      not with -A, -E, -S or -B\n",
+          "      not with -A, -E, -S or -B\n"
+          "  -G: global-local search, end to end in the query (q), the record (t) or both (b);\n"
+          "      implies -g; not with -A, -E, -S, -X or -F\n",
           argv0);
 }
 
@@ -257,14 +267,14 @@ static int print_alignments(FILE *out, sw_bank *bank, const uint8_t *res, size_t
 int main(int argc, char **argv) {
   const char *qpath = NULL, *lpath = NULL, *opath = NULL, *pen = NULL, *rpath = NULL;
   int protein = 0, gotoh = 0, device = -1, transcript = 0, best = 0, both = 0, xlate = 0, opt;
-  int ndev = 0, devs[SW_MAX_DEVICES], fshift = 0;
+  int ndev = 0, devs[SW_MAX_DEVICES], fshift = 0, glocal = 0;
   long nalign = 0, fs = 0;
   int have_stats = 0; /* 1: -S (given), 2: -E (estimated) */
   unsigned long stat_rounds = 0;
   unsigned long long stat_seed = 0;
   sw_statistics stats;
   memset(&stats, 0, sizeof(stats));
-  while ((opt = getopt(argc, argv, "q:l:p:Pgd:o:TR:bA:E:S:BXF:h")) != -1) {
+  while ((opt = getopt(argc, argv, "q:l:p:Pgd:o:TR:bA:E:S:BXF:G:h")) != -1) {
     switch (opt) {
       case 'q': qpath = optarg; break;
       case 'l': lpath = optarg; break;
@@ -297,6 +307,17 @@ int main(int argc, char **argv) {
         fshift = gotoh = 1;
         break;
       }
+      case 'G':
+        glocal = !strcmp(optarg, "q")   ? SW_ENDS_QUERY
+                 : !strcmp(optarg, "t") ? SW_ENDS_TARGET
+                 : !strcmp(optarg, "b") ? SW_ENDS_BOTH
+                                        : 0;
+        if (!glocal) {
+          fprintf(stderr, "-G takes q (query end to end), t (record end to end) or b (both)\n");
+          return usage(argv[0]), 1;
+        }
+        gotoh = 1;
+        break;
       case 'A': {
         char *end;
         nalign = strtol(optarg, &end, 10);
@@ -340,6 +361,18 @@ int main(int argc, char **argv) {
         : have_stats ? "-F: statistics of shifted scores do not exist yet: not with -E or -S"
         : both       ? "-F searches both strands already: not with -B"
                      : NULL;
+    if (why) {
+      fprintf(stderr, "%s\n", why);
+      usage(argv[0]);
+      return 1;
+    }
+  }
+  if (glocal) {
+    const char *why =
+        xlate || fshift ? "-G: the translated searches are local: not with -X or -F"
+        : nalign > 0    ? "-G: alignments of global-local hits do not exist yet: not with -A"
+        : have_stats    ? "-G: statistics of global-local scores do not exist yet: not with -E or -S"
+                        : NULL;
     if (why) {
       fprintf(stderr, "%s\n", why);
       usage(argv[0]);
@@ -427,6 +460,8 @@ int main(int argc, char **argv) {
     st = fshift ? sw_score_fshift(bank, res, total, offs, lens, lib.n, NULL, (int32_t)fs, scores,
                                   strands)
          : xlate ? sw_score_frames(bank, res, total, offs, lens, lib.n, NULL, scores, frames)
+         : glocal ? sw_score_glocal(bank, res, total, offs, lens, lib.n, glocal, both, scores,
+                                    NULL, strands)
          : both ? sw_score_strands(bank, res, total, offs, lens, lib.n, scores, strands)
                 : sw_score_batch(bank, res, total, offs, lens, NULL, lib.n, scores);
   if (st == SW_OK && have_stats == 2 && lib.n && xlate) {
@@ -491,9 +526,9 @@ int main(int argc, char **argv) {
   if (opath) fclose(out);
   uint64_t bid = 0;
   int32_t bsc = 0;
-  /* (-B and -X track no best hit on the device: the lowest index with the best merged score) */
+  /* (-B, -X and -G track no best hit on the device: the lowest index with the best merged score) */
   if (best && lib.n &&
-      (both || xlate ? sw_best_hit(bank, scores, NULL, lib.n, &bid, &bsc)
+      (both || xlate || glocal ? sw_best_hit(bank, scores, NULL, lib.n, &bid, &bsc)
                      : sw_batch_best(bank, &bid, &bsc, NULL)) == SW_OK)
     fprintf(stderr, "best: >%s score: %d%s\n", lib.names[bid], bsc,
             strands ? (strands[bid] ? " [r]" : " [f]")

@@ -59,6 +59,7 @@ EXPORTS = (
     "sw_score_fshift", "sw_score_fshift_device",
     "sw_align_fshift_hits", "sw_align_fshift_hits_device",
     "sw_estimate_fshift_statistics", "sw_estimate_fshift_statistics_device",
+    "sw_score_glocal", "sw_score_glocal_device",
 )
 ABI_VERSION = 6
 COUNTERS = ("stream_calls", "stream_reruns", "stream_declined", "chunked_calls", "device_sorts",
@@ -77,6 +78,9 @@ _ALIGN_WHERE = ALIGN_REVERSE | ALIGN_FRAME_MASK  # (flags that say where a hit l
 FRAME_COUNT = 6                              # SW_FRAME_COUNT: reading frames of a DNA target
 FRAME_TAGS = ("+1", "+2", "+3", "-1", "-2", "-3")
 FSHIFT_MAX_QUERY = 1024                      # SW_FSHIFT_MAX_QUERY: query rows of score_frameshift
+GLOCAL_MAX_QUERY = 1024                      # SW_GLOCAL_MAX_QUERY: query rows of score_glocal
+ENDS_QUERY, ENDS_TARGET, ENDS_BOTH = 1, 2, 3  # SW_ENDS_*: what score_glocal aligns end to end
+END_NONE = 0xFFFFFFFF                        # SW_END_NONE: the score is the boundary's
 STANDARD_CODE = "FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG"
 RECORD_BYTES, RECORD_MAX_BASES = 64, 232
 TOP_MAX_K = 4096                             # SW_TOP_MAX_K: the largest k of the top-hits calls
@@ -295,6 +299,8 @@ def lib() -> ctypes.CDLL:
                                              P]),
         "sw_score_fshift": (i32, [P, P, sz, P, P, sz, P, i32, P, P]),
         "sw_score_fshift_device": (i32, [P, P, P, P, sz, u32, P, i32, P, P, P]),
+        "sw_score_glocal": (i32, [P, P, sz, P, P, sz, i32, i32, P, P, P]),
+        "sw_score_glocal_device": (i32, [P, P, P, P, sz, u32, i32, i32, P, P, P, P]),
         "sw_align_fshift_hits": (i32, [P, P, sz, P, P, P, sz, P, i32, P, sz, P, sz, P, P, sz, P]),
         "sw_align_fshift_hits_device": (i32, [P, P, P, P, P, sz, u32, P, i32, P, sz, P, sz, P, P,
                                               u32, P]),
@@ -1002,6 +1008,35 @@ class ScoreBank:
         scores = sc[:nq * n].reshape(nq, n)
         strands = sd[:nq * n].reshape(nq, n)
         return (scores[0], strands[0]) if nq == 1 else (scores, strands)
+
+    # the global-local search: the query, the target or both scored end to end
+    def score_glocal_device(self, d_res: int, d_offs: int, d_lens: int, n: int, max_len: int,
+                            ends: int, d_scores: int, d_end_pos: int = 0, d_strands: int = 0,
+                            both_strands: bool = False, stream: int = 0):
+        """sw_score_glocal_device: device pointers (ints); d_scores receives the nq x n int32
+        scores of the batch under `ends` (ENDS_QUERY, ENDS_TARGET, ENDS_BOTH), d_end_pos
+        (optional) the nq x n uint32 end positions (END_NONE: the boundary), d_strands (optional)
+        the nq x n uint8 strands.  Async on `stream`."""
+        self._check(lib().sw_score_glocal_device(
+            self._h, d_res or None, d_offs or None, d_lens or None, n, max_len, ends,
+            1 if both_strands else 0, d_scores or None, d_end_pos or None, d_strands or None,
+            stream or None))
+
+    def score_glocal(self, targets, ends: int, both_strands: bool = False):
+        """sw_score_glocal: (scores int32, end positions uint32, strands uint8) of host targets,
+        [n] for one loaded query, [nq, n] for a query set.  `targets`: a sequence of code arrays,
+        or a packed batch as the tuple (residues, offsets, lens)."""
+        if not (isinstance(targets, tuple) and len(targets) == 3):
+            targets = pack_targets([np.asarray(t, np.uint8) for t in targets])
+        res, offs, ln, _ = validate_batch(*targets)
+        nq, n = max(self.query_count(), 1), len(ln)
+        sc = np.zeros(nq * max(n, 1), np.int32)
+        ep = np.zeros(nq * max(n, 1), np.uint32)
+        sd = np.zeros(nq * max(n, 1), np.uint8)
+        self._check(lib().sw_score_glocal(self._h, _p(res), res.size, _p(offs), _p(ln), n, ends,
+                                          1 if both_strands else 0, _p(sc), _p(ep), _p(sd)))
+        out = tuple(a[:nq * n].reshape(nq, n) for a in (sc, ep, sd))
+        return tuple(a[0] for a in out) if nq == 1 else out
 
     def estimate_frameshift_statistics_device(self, d_dna: int, d_offs: int, d_lens: int, n: int,
                                               max_len: int, frameshift: int, seed: int = 0,
