@@ -97,7 +97,9 @@ extern "C" {
  *        of frameshift hits -- sw_align_fshift_hits[_device], SW_CIGAR_FS_SKIP / _BACK; (test
  *        SWBANK_HAS_FSHIFT_STATS) their statistics -- sw_estimate_fshift_statistics[_device];
  *        (test SWBANK_HAS_GLOCAL) the global-local search -- sw_score_glocal[_device],
- *        SW_ENDS_QUERY / _TARGET / _BOTH, SW_END_NONE, SW_GLOCAL_MAX_QUERY. */
+ *        SW_ENDS_QUERY / _TARGET / _BOTH, SW_END_NONE, SW_GLOCAL_MAX_QUERY; (test
+ *        SWBANK_HAS_GLOCAL_ALIGN) alignments of global-local hits --
+ *        sw_align_glocal_hits[_device]. */
 #define SWBANK_ABI_VERSION 6
 #define SWBANK_HAS_ALIGN 1
 #define SWBANK_HAS_TOPK 1
@@ -417,7 +419,9 @@ sw_status sw_best_queries(sw_bank *bank, const int32_t *scores, size_t n, size_t
  * Inputs are byte codes only (no records, no packed codes). */
 enum { SW_CIGAR_M = 0, SW_CIGAR_I = 1, SW_CIGAR_D = 2 };  /* BAM codes: I consumes query only,
                                                              D consumes target only          */
-enum { SW_ALIGN_EMPTY = 1,    /* score 0: no alignment, all coordinates 0, no CIGAR          */
+enum { SW_ALIGN_EMPTY = 1,    /* score 0: no alignment, all coordinates 0, no CIGAR (for
+                                 sw_align_glocal_hits*: the boundary won; the score is the
+                                 boundary's value and may be negative)                        */
        SW_ALIGN_NO_PATH = 2 };/* coordinates valid, CIGAR not produced (window over budget
                                  or the caller's CIGAR space too small)                      */
 typedef struct sw_alignment {
@@ -1124,6 +1128,78 @@ sw_status sw_score_glocal(sw_bank *bank, const uint8_t *residues, size_t residue
                           const uint64_t *offsets, const uint32_t *lens, size_t n, int32_t ends,
                           int32_t both_strands, int32_t *scores_out, uint32_t *end_pos_out,
                           uint8_t *strands_out);
+
+/* ---- alignments of global-local hits (ABI 6 addition) ------------------------------------------
+ * Where a pair of sw_score_glocal aligns: the start, a CIGAR and the identities.  The pair list,
+ * SW_ALIGN_NO_PATH, the SW_ALIGN_NO_HIT sentinel slots, the cigar_offset layouts, the packed host
+ * layout, the SWBANK_ALIGN_MB budget and its chunks are sw_align_set_hits[_device]'s.
+ * sw_align_set_hits itself cannot stand in: it aligns the best local piece, floored at 0, which
+ * is another alignment with another score.
+ *
+ * Everything is stated on the strand walked, c[0..L): the target or rc(target).  H, E, F and the
+ * boundaries are those of "global-local search" above for the call's `ends`; a path runs from a
+ * boundary cell to the end cell.
+ *   score   what sw_score_glocal returns for the pair; the forward strand unless the reverse
+ *           strand is strictly better (then flags |= SW_ALIGN_REVERSE).
+ *   end     the score call's end position: QUERY the cell (m-1, j_end), the smallest such j;
+ *           TARGET (i_end, L-1), the smallest such i; BOTH (m-1, L-1).  The end cell is walked in
+ *           state H, not forced to M: a query tail may lie against a gap.
+ *   start   the boundary cell the path leaves from.  QUERY: a cell (-1, c), -1 <= c < j_end;
+ *           among the c for which a path from (-1, c) to the end cell scores `score` -- which is
+ *           to say that the BOTH score of q against c[c+1 .. j_end] equals `score`; no c gives
+ *           more -- the largest is taken, and t_start = c + 1.  TARGET: the transpose, the largest
+ *           r gives q_start = r + 1.  BOTH: (-1, -1).
+ *   CIGAR   an optimal path of the anchored matrix over the window [q_start..q_end] x
+ *           [t_start..t_end]: both boundaries penalised, no floor; its value at the last cell is
+ *           `score`.  An op is len << 4 | code with the codes M, I, D above, adjacent equal codes
+ *           merged.  The first and the last op need NOT be M ("3I40M", "40M2I").  The ops consume
+ *           exactly the window's rows and columns, and re-scoring them gives `score`: a gap run of
+ *           k columns costs open + k * extend, a run being a maximal stretch of one code.  Walking
+ *           back from the end cell: the diagonal (M) first, then a gap from the left (D), then a
+ *           gap from above (I); a gap run opens rather than extends when both are optimal; on
+ *           reaching row -1 the rest of the path is D ops, on column -1 I ops.  n_columns = M + I
+ *           + D columns; n_identities = M columns with equal codes, the complemented code on the
+ *           reverse strand.
+ *   record  ends     q_start  q_end  t_start  t_end
+ *           QUERY    0        m-1    c+1      j_end
+ *           TARGET   r+1      i_end  0        L-1
+ *           BOTH     0        m-1    0        L-1
+ *           A reverse hit reports t_start = L-1 - t_end' and t_end = L-1 - t_start' of the strand
+ *           walked, as sw_align_strand_hits does; its CIGAR runs along the strand walked.
+ *   empty   the boundary won: SW_END_NONE under QUERY or TARGET, L = 0 under BOTH.  The record is
+ *           SW_ALIGN_EMPTY with `score` the boundary's value, which may be negative; every
+ *           coordinate and count is 0 and there are no ops.  An empty pair is never reverse (both
+ *           strands tie).  For these calls SW_ALIGN_EMPTY therefore means "no cell aligned", not
+ *           "score 0", and a record with a path may score 0 or less.
+ *
+ * Limits and refusals are sw_score_glocal's, in its order (both_strands on a protein bank, the
+ * gap model, ends, the state, the query length); then a latched hand-off fault (the device form),
+ * the multi-device bank running on its root, n_hits == 0 (SW_OK), a NULL buffer or n == 0
+ * (SW_ERR_ARG), the pair list's checks, n_hits x cigar_stride >= 2^32 (SW_ERR_ARG), and the
+ * SW_ERR_RANGE rules of sw_score_glocal with the caller's max_len (the host form: the longest
+ * listed target, after its SW_ERR_ARG checks of the listed targets).  Nothing is written by a
+ * refused call.  The device form sizes its direction-store slots from max_len x the longest
+ * query and validates nothing it would have to read back; the host form gathers only the listed
+ * targets, checks their codes against the bank's alphabet and plans its chunks from the actual
+ * windows.  sw_last_kernel reports "align-glocal i32 ends=<e> nq=<nq> hits=<n_hits> chunks=<c>";
+ * with sw_bank_set_timing the end / start passes and the path passes are bracketed as one launch
+ * each. */
+#define SWBANK_HAS_GLOCAL_ALIGN 1
+
+sw_status sw_align_glocal_hits_device(sw_bank *bank, const uint8_t *d_residues,
+                                      const uint64_t *d_offsets, const uint32_t *d_lens,
+                                      const uint64_t *d_ids, size_t n, uint32_t max_len,
+                                      int32_t ends, int32_t both_strands,
+                                      const uint32_t *d_hit_queries, size_t hits_per_query,
+                                      const uint64_t *d_hits, size_t n_hits, sw_alignment *d_out,
+                                      uint32_t *d_cigar, uint32_t cigar_stride, void *stream);
+
+sw_status sw_align_glocal_hits(sw_bank *bank, const uint8_t *residues, size_t residues_len,
+                               const uint64_t *offsets, const uint32_t *lens,
+                               const uint64_t *ids, size_t n, int32_t ends, int32_t both_strands,
+                               const uint32_t *hit_queries, size_t hits_per_query,
+                               const uint64_t *hits, size_t n_hits, sw_alignment *out,
+                               uint32_t *cigar, size_t cigar_cap, size_t *cigar_used);
 
 /* ---- profiling(≙ the CAPI AFU's cycle counters, capi_sample_aligner/hdl-verliog/afu.v
  *      _DEBUGGING_ "calculation #N completed, runtime: C cycles") ------------------------- */

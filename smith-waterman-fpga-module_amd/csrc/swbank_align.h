@@ -101,6 +101,40 @@ hipError_t swk_launch_fsalign_ends(const SwkFsAlign* p, hipStream_t st);
 hipError_t swk_launch_fsalign_paths(const SwkFsAlign* p, const uint32_t* list, size_t h0,
                                     size_t count, const SwkAlignPlan* plan, uint64_t slot,
                                     uint32_t* dirs, hipStream_t st);
+
+/* Alignments of global-local hits (swbank_kglalign.hip): one call's arguments.  The
+ * batch and the pair list as for SwkFsAlign (any alphabet of at most 24 codes; both != 0: DNA
+ * codes); ends: SW_ENDS_*; o = open + extend, e <= 0, inside the range rule of sw_score_glocal
+ * for max_len. */
+typedef struct SwkGlAlign {
+  const uint8_t* res;
+  const uint64_t* offs;
+  const uint32_t* lens;
+  const uint64_t* ids;
+  const uint64_t* hits;
+  size_t n_hits, n;
+  uint32_t max_len; /* codes of a target past it are not read */
+  const uint2* qtab;
+  const int8_t* mat;
+  const uint8_t* query;
+  uint32_t nq, qlen, alpha;
+  const uint32_t* hit_queries;
+  uint32_t hits_per_query;
+  int32_t o, e, ends, both;
+  void* out; /* sw_alignment[n_hits] */
+  uint32_t* cigar;
+  uint32_t cigar_stride;
+} SwkGlAlign;
+
+/* Dwords of direction store a window of rows x cols cells takes under the rows per lane K of
+ * queries of at most qlen rows: (cols + ceil(rows / K) - 1) steps x K bytes x 64 lanes. */
+uint64_t swk_glalign_dir_dwords(uint32_t qlen, uint32_t rows, uint32_t cols);
+/* Passes A and B for hits [0, n_hits): every record written, paths left out. */
+hipError_t swk_launch_glalign_ends(const SwkGlAlign* p, hipStream_t st);
+/* Passes C and D for `count` positions, placed as swk_launch_align_paths places them. */
+hipError_t swk_launch_glalign_paths(const SwkGlAlign* p, const uint32_t* list, size_t h0,
+                                    size_t count, const SwkAlignPlan* plan, uint64_t slot,
+                                    uint32_t* dirs, hipStream_t st);
 #ifdef __cplusplus
 }
 #endif

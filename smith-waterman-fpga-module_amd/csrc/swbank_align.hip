@@ -4,7 +4,9 @@
 // §3.13), the chunking of the direction store, the host calls' staging.  All entries run the same
 // code; they differ in the pair list.  The kernels are in
 // swbank_kalign.hip.  The alignments of frameshift hits (sw_align_fshift_hits*, DESIGN.md §3.16,
-// at the end of the file) run the same scaffolding around the kernels of swbank_kfsalign.hip.
+// behind them) run the same scaffolding around the kernels of swbank_kfsalign.hip, and so do the
+// alignments of global-local hits (sw_align_glocal_hits*, DESIGN.md §3.18, at the end of the file)
+// around the kernels of swbank_kglalign.hip.
 #include "swbank_bank.h"
 
 namespace {
@@ -353,7 +355,9 @@ Windows plan_windows(const sw_alignment* out, size_t n_hits, uint64_t budget, D&
   uint64_t used = 0;
   for (size_t h = 0; h < n_hits; ++h) {
     const sw_alignment& r = out[h];
-    if (r.score <= 0) continue;
+    // (no window; for the local calls this is score <= 0, a global-local hit with a path may
+    // score 0 or less)
+    if (r.flags & SW_ALIGN_EMPTY) continue;
     const uint32_t Q = r.q_end - r.q_start + 1, L = r.t_end - r.t_start + 1;
     const uint64_t need = dwords(Q, L);
     if (need > budget) continue;  // SW_ALIGN_NO_PATH, coordinates stay
@@ -914,5 +918,170 @@ extern "C" sw_status sw_align_fshift_hits(sw_bank* b, const uint8_t* residues, s
       out, cigar, cigar_cap, cigar_used, chunks);
   if (st != SW_OK) return st;
   name_fshift(b, n_hits, chunks);
+  return SW_OK;
+}
+
+// ---- alignments of global-local hits -----------------------------------------
+// Hit h (query i, target k) is aligned as sw_score_glocal scores it, by the kernels of
+// swbank_kglalign.hip, which read the batch as it lies and write the whole record (strand, the
+// forward target's coordinates) themselves; the pair list, the chunks of the direction store and
+// the host form's staging are the code above.
+namespace {
+
+// The launch block over a batch and a pair list already on the device.
+SwkGlAlign glocal_block(sw_bank* b, int32_t ends, int32_t both_strands, const uint8_t* d_res,
+                        const uint64_t* d_offs, const uint32_t* d_lens, const uint64_t* d_ids,
+                        size_t n, uint32_t max_len, const uint32_t* d_hit_queries,
+                        size_t hits_per_query, const uint64_t* d_hits, size_t n_hits,
+                        void* d_out) {
+  const size_t nq = query_count(b);
+  SwkGlAlign f{};
+  f.res = d_res;
+  f.offs = d_offs;
+  f.lens = d_lens;
+  f.ids = d_ids;
+  f.hits = d_hits;
+  f.n_hits = n_hits;
+  f.n = n;
+  f.max_len = max_len;
+  f.qtab = reinterpret_cast<const uint2*>(b->al_tab.p);
+  f.mat = reinterpret_cast<const int8_t*>(b->al_tab.p + nq * sizeof(uint2));
+  f.query = b->al_tab.p + nq * sizeof(uint2) + b->matrix.size();
+  f.nq = (uint32_t)nq;
+  f.qlen = (uint32_t)b->query.size();  // (a set: its longest query)
+  f.alpha = (uint32_t)b->alpha;
+  f.hit_queries = d_hit_queries;
+  f.hits_per_query = (uint32_t)hits_per_query;
+  f.o = b->gap_open + b->gap_extend;
+  f.e = b->gap_extend;
+  f.ends = ends;
+  f.both = both_strands ? 1 : 0;
+  f.out = d_out;
+  return f;
+}
+
+// The bank after the argument checks: prepare()d, inside the range rule of sw_score_glocal for
+// targets of at most max_len codes, the queries' table on the device.  The rule bounds every cell
+// of a matrix of at most 1,024 rows and max_len columns with penalised boundaries; the reversed
+// walk of pass B and the window of pass C are such matrices (both boundaries penalised, which is
+// the case the rule is stated for), so it covers them.
+sw_status glocal_ready(sw_bank* b, const char* what, uint32_t max_len) {
+  sw_status st = prepare(b);
+  if (st != SW_OK) return st;
+  if (!glocal_in_range(b, max_len))
+    return fail(b, SW_ERR_RANGE,
+                "%s: |open + extend| + (%d + 64 + max_len %u) x max(|extend|, 128) reaches 2^30",
+                what, SW_GLOCAL_MAX_QUERY, max_len);
+  if ((size_t)b->alpha * b->alpha != b->matrix.size() || b->alpha > SW_PROTEIN_ALPHA)
+    return fail(b, SW_ERR_UNSUPPORTED, "%s: alphabet %d too large", what, b->alpha);
+  return prepare_align(b);
+}
+
+void name_glocal(sw_bank* b, int32_t ends, size_t hits, size_t chunks) {
+  snprintf(b->last_kernel, sizeof(b->last_kernel),
+           "align-glocal i32 ends=%d nq=%zu hits=%zu chunks=%zu", ends, query_count(b), hits,
+           chunks);
+}
+
+}  // namespace
+
+extern "C" sw_status sw_align_glocal_hits_device(sw_bank* b, const uint8_t* d_res,
+                                                 const uint64_t* d_offs, const uint32_t* d_lens,
+                                                 const uint64_t* d_ids, size_t n, uint32_t max_len,
+                                                 int32_t ends, int32_t both_strands,
+                                                 const uint32_t* d_hit_queries,
+                                                 size_t hits_per_query, const uint64_t* d_hits,
+                                                 size_t n_hits, sw_alignment* d_out,
+                                                 uint32_t* d_cigar, uint32_t cigar_stride,
+                                                 void* stream) {
+  DevGuard dev_guard(b);  // on the bank's device; the caller's is restored on return (ABI 6)
+  if (!b) return SW_ERR_ARG;
+  sw_status st = glocal_opening(b, "sw_align_glocal_hits_device", ends, both_strands);
+  if (st != SW_OK) return st;
+  // a hand-off fault latched by an earlier device call is returned before anything runs
+  if (const sw_status fs = take_fault(b, 0); fs != SW_OK) return fs;
+  if (on_root(b, stream, st, [&](sw_bank* r, void* s) {
+        return sw_align_glocal_hits_device(r, d_res, d_offs, d_lens, d_ids, n, max_len, ends,
+                                           both_strands, d_hit_queries, hits_per_query, d_hits,
+                                           n_hits, d_out, d_cigar, cigar_stride, s);
+      }))
+    return st;
+  if (n_hits == 0) return SW_OK;
+  if (!d_res || !d_offs || !d_lens || !d_out || n == 0)
+    return fail(b, SW_ERR_ARG, "null device buffer or an empty batch");
+  const Pairs pr{true, d_hit_queries, hits_per_query, d_hits, n_hits};
+  if ((st = check_pairs(b, pr, n)) != SW_OK) return st;
+  if (d_cigar && cigar_stride && (uint64_t)n_hits * cigar_stride > 0xFFFFFFFFull)
+    return fail(b, SW_ERR_ARG, "n_hits x cigar_stride must fit 32 bits (cigar_offset)");
+  if ((st = glocal_ready(b, "sw_align_glocal_hits_device", max_len)) != SW_OK) return st;
+  HIPOK(b, hipSetDevice(b->device));
+  hipStream_t hs = stream_or(b, stream);
+  SwkGlAlign f = glocal_block(b, ends, both_strands, d_res, d_offs, d_lens, d_ids, n, max_len,
+                              d_hit_queries, hits_per_query, d_hits, n_hits, d_out);
+  f.cigar = d_cigar;
+  f.cigar_stride = d_cigar ? cigar_stride : 0;
+  HIPOK(b, hipStreamWaitEvent(hs, b->ev_ready, 0));  // the queries' codes are uploaded
+  HIPOK(b, hipStreamWaitEvent(hs, b->ev_used, 0));   // bank scratch is free
+  st = timed_on(b, hs, [&] { return swk_launch_glalign_ends(&f, hs); });
+  size_t chunks = 0;
+  if (st == SW_OK && f.cigar_stride) {
+    const uint64_t slot = swk_glalign_dir_dwords(f.qlen, f.qlen, max_len);
+    st = paths_in_slots(b, n_hits, slot, hs, chunks, [&](size_t h0, size_t count) {
+      return swk_launch_glalign_paths(&f, nullptr, h0, count, nullptr, slot, b->al_dirs.p, hs);
+    });
+  }
+  // whatever was launched reads the table and the scratch: the next use is ordered after it
+  const hipError_t er = hipEventRecord(b->ev_used, hs);
+  if (st != SW_OK) return st;
+  HIPOK(b, er);
+  name_glocal(b, ends, n_hits, chunks);
+  return SW_OK;
+}
+
+extern "C" sw_status sw_align_glocal_hits(sw_bank* b, const uint8_t* residues, size_t residues_len,
+                                          const uint64_t* offsets, const uint32_t* lens,
+                                          const uint64_t* ids, size_t n, int32_t ends,
+                                          int32_t both_strands, const uint32_t* hit_queries,
+                                          size_t hits_per_query, const uint64_t* hits,
+                                          size_t n_hits, sw_alignment* out, uint32_t* cigar,
+                                          size_t cigar_cap, size_t* cigar_used) {
+  DevGuard dev_guard(b);  // on the bank's device; the caller's is restored on return (ABI 6)
+  if (!b) return SW_ERR_ARG;
+  if (cigar_used) *cigar_used = 0;
+  sw_status st = glocal_opening(b, "sw_align_glocal_hits", ends, both_strands);
+  if (st != SW_OK) return st;
+  if (on_root(b, nullptr, st, [&](sw_bank* r, void*) {  // (hit lists are small)
+        return sw_align_glocal_hits(r, residues, residues_len, offsets, lens, ids, n, ends,
+                                    both_strands, hit_queries, hits_per_query, hits, n_hits, out,
+                                    cigar, cigar_cap, cigar_used);
+      }))
+    return st;
+  if (n_hits == 0) return SW_OK;
+  if (!offsets || !lens || !out) return fail(b, SW_ERR_ARG, "null host buffer");
+  const Pairs pr{true, hit_queries, hits_per_query, hits, n_hits};
+  if ((st = check_pairs(b, pr, n)) != SW_OK) return st;
+  // (alpha is the bank's before prepare(): the gathering checks the listed targets' codes)
+  Gathered g;
+  if ((st = gather_hits(b, residues, residues_len, offsets, lens, n, pr, g)) != SW_OK) return st;
+  if ((st = glocal_ready(b, "sw_align_glocal_hits", g.max_len)) != SW_OK) return st;
+  HIPOK(b, hipSetDevice(b->device));
+  hipStream_t hs = b->stream;
+  SwkAlign p{};  // (the staged buffers only: no launch block, no scratch rows)
+  if ((st = stage_hits(b, pr, g, p, hs, false)) != SW_OK) return st;
+  // hit h is target h of the gathered batch against query al_hq[h]
+  SwkGlAlign f = glocal_block(b, ends, both_strands, p.res, p.offs, p.lens, nullptr, n_hits,
+                              g.max_len, p.hit_queries, 0, nullptr, n_hits, p.out);
+  size_t chunks = 0;
+  st = host_passes(
+      b, pr, g, ids, hs, [&](hipStream_t s) { return swk_launch_glalign_ends(&f, s); },
+      [&](const uint32_t* list, size_t count, const SwkAlignPlan* plan, hipStream_t s) {
+        f.cigar = b->al_cig.p;
+        f.cigar_stride = 1;  // (places come from the plan)
+        return swk_launch_glalign_paths(&f, list, 0, count, plan, 0, b->al_dirs.p, s);
+      },
+      [&](uint32_t Q, uint32_t L) { return swk_glalign_dir_dwords(f.qlen, Q, L); }, out, cigar,
+      cigar_cap, cigar_used, chunks);
+  if (st != SW_OK) return st;
+  name_glocal(b, ends, n_hits, chunks);
   return SW_OK;
 }

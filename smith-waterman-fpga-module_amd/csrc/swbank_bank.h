@@ -1028,6 +1028,10 @@ sw_status prepare_align(sw_bank* b);
 // state, query length), in the header's order
 sw_status fshift_opening(sw_bank* b, const char* what, const uint8_t* codon_table,
                          int32_t frameshift, uint8_t tab[64]);
+// ---- swbank_glocal.hip: what a global-local entry checks first (strands, model, ends, state,
+// query length), in the header's order, and its range rule for targets of at most max_len codes
+sw_status glocal_opening(sw_bank* b, const char* what, int32_t ends, int32_t both_strands);
+bool glocal_in_range(const sw_bank* b, uint32_t max_len);
 // ---- swbank_launch.hip (device batches against a query set; sstride: between query rows)
 sw_status launch_set(sw_bank* b, const uint8_t* d_res, const uint64_t* d_offs,
                      const uint32_t* d_lens, size_t n, uint32_t min_len, uint32_t max_len,

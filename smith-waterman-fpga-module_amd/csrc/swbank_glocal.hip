@@ -7,8 +7,9 @@
 // frame search's host buffers and its end positions in gl_hend (both calls synchronise).
 #include "swbank_bank.h"
 
-// What both entries check before anything else, in the order of the header's list.
-static sw_status glocal_opening(sw_bank* b, const char* what, int32_t ends, int32_t both_strands) {
+// What both entries (and the aligner's, swbank_align.hip) check before anything else, in the
+// order of the header's list.
+sw_status glocal_opening(sw_bank* b, const char* what, int32_t ends, int32_t both_strands) {
   if (both_strands && b->cfg.alphabet != SW_ALPHABET_DNA)
     return fail(b, SW_ERR_UNSUPPORTED, "%s: both_strands on DNA banks only", what);
   if (!b->gotoh())
@@ -25,7 +26,7 @@ static sw_status glocal_opening(sw_bank* b, const char* what, int32_t ends, int3
 }
 
 // The range rule of the header: no cell, pad rows and lanes past the target included, leaves int32.
-static bool glocal_in_range(const sw_bank* b, uint32_t max_len) {
+bool glocal_in_range(const sw_bank* b, uint32_t max_len) {
   const int64_t o = std::llabs((int64_t)b->gap_open + b->gap_extend);
   const int64_t e = std::max<int64_t>(std::llabs((int64_t)b->gap_extend), 128);
   return o + (SW_GLOCAL_MAX_QUERY + 64 + (int64_t)max_len) * e < ((int64_t)1 << 30);

@@ -1,5 +1,6 @@
-// swbank_kglwalk.h — the walk of the global-local search's score kernel (swbank_kglocal.hip);
-// include/swbank.h "global-local search", DESIGN.md §3.17.
+// swbank_kglwalk.h — the walk of the global-local search's score kernel (swbank_kglocal.hip) and
+// of the aligner of its hits (swbank_kglalign.hip); include/swbank.h "global-local search",
+// DESIGN.md §3.17 and §3.18.
 //
 // A wave walks one matrix: the m rows of a query against the L columns of a strand, under the
 // Gotoh recurrence WITHOUT a floor and with the penalised boundaries that `ENDS` selects.  Lane l
@@ -34,6 +35,11 @@
 //     greater in row order; H(-1,L-1) is lane 0's start.  BOTH: that step, row m - 1 alone.
 //     Positions are kept as index + 1, so the boundary (index -1) is 0 and wins every tie; the
 //     lanes are merged by value, then by the smaller position.
+//
+// The aligner of global-local hits (swbank_kglalign.hip) runs the same walk in
+// two more modes (GlMode): `Anchored` penalises both boundaries whatever ENDS says and takes the
+// result as ENDS does (QUERY: the last row; TARGET: the last column), which is what finds a hit's
+// start on the reversed rows and columns; `Dirs` (ENDS = BOTH) stores one direction byte per cell.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -54,16 +60,32 @@ __device__ __forceinline__ int32_t gl_shr1(int32_t lane0_value, int32_t v) {  //
 
 // prof[c][row], row < 64K: the score of query row `row` against target code c < alpha; GL_PAD past
 // the query.  All `nthreads` threads of the workgroup call it; the caller synchronises.
-template <int K>
+// STEP = -1 reads the query backwards from qp (the rows of a reversed walk).
+template <int K, int STEP = 1>
 __device__ __forceinline__ void gl_profile(const int8_t* mat, uint32_t alpha, int8_t* prof,
                                            const uint8_t* qp, uint32_t rows, uint32_t nthreads) {
   constexpr int ROWS = 64 * K;
   for (uint32_t row = threadIdx.x; row < (uint32_t)ROWS; row += nthreads) {
     const bool in_q = row < rows;
-    const uint32_t q = in_q ? qp[row] : 0u;
+    const uint32_t q = in_q ? qp[STEP == 1 ? (int32_t)row : STEP * (int32_t)row] : 0u;
     const int8_t* mr = mat + (q < alpha ? q : alpha - 1) * alpha;
     for (uint32_t c = 0; c < alpha; ++c) prof[c * ROWS + row] = in_q ? mr[c] : (int8_t)GL_PAD;
   }
+}
+
+// Score: the search's walk, boundaries and result by ENDS.  Anchored: both boundaries penalised,
+// the result where ENDS takes it.  Dirs: the anchored matrix (ENDS = GL_BOTH) with one direction
+// byte per cell, stored by walk step: at step t lane l writes its K bytes as K / 4 dwords at
+// dirs[t][word][lane], one coalesced store per word.
+enum class GlMode { Score, Anchored, Dirs };
+// A direction byte: bits 0-1 the source of H (M, then E, then F on a tie), GL_E_EXT / GL_F_EXT:
+// E / F extends (strictly better than opening: a gap run opens when both are optimal).
+constexpr uint32_t GL_SRC_M = 0, GL_SRC_E = 1, GL_SRC_F = 2, GL_E_EXT = 16, GL_F_EXT = 32;
+
+// Dwords of direction store a window of rows x cols cells takes at K rows per lane.
+__host__ __device__ inline uint64_t gl_dir_dwords(int K, uint32_t rows, uint32_t cols) {
+  if (rows == 0 || cols == 0) return 0;
+  return ((uint64_t)cols + ((uint64_t)rows + K - 1) / K - 1) * (uint64_t)(K / 4) * 64;
 }
 
 struct GlBest {
@@ -73,12 +95,15 @@ struct GlBest {
 
 // The walk of one wave over m rows (1 <= m <= 64K, the profile's) and L columns; code(j), j < L,
 // is the strand's code at column j (< alpha).  The same result in every lane.
-template <int K, int ENDS, class Code>
+template <int K, int ENDS, GlMode MODE = GlMode::Score, class Code>
 __device__ __forceinline__ GlBest gl_walk(const int8_t* prof, const Code& code, uint32_t L,
-                                          uint32_t m, int32_t o, int32_t e) {
+                                          uint32_t m, int32_t o, int32_t e,
+                                          uint32_t* dirs = nullptr) {
   constexpr int ROWS = 64 * K;
-  constexpr bool QB = ENDS != GL_TARGET;  // the query's boundary column is penalised
-  constexpr bool TB = ENDS != GL_QUERY;   // the target's boundary row is penalised
+  constexpr bool SCORE = MODE == GlMode::Score, DIRS = MODE == GlMode::Dirs;
+  static_assert(!DIRS || ENDS == GL_BOTH, "the direction store is the anchored matrix's");
+  constexpr bool QB = !SCORE || ENDS != GL_TARGET;  // the query's boundary column is penalised
+  constexpr bool TB = !SCORE || ENDS != GL_QUERY;   // the target's boundary row is penalised
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t nl = (m + K - 1) / K;  // lanes that hold rows
   const uint32_t steps = L ? L + nl - 1 : 0u;
@@ -124,12 +149,25 @@ __device__ __forceinline__ GlBest gl_walk(const int8_t* prof, const Code& code, 
         // seven VALU a cell: H + o is formed once and opens both the gap to the right (the next
         // step's E) and the gap below (the next row's F)
         int32_t no = un + o, f = uf, d = ud;
+        uint32_t dw[K / 4];
+        if constexpr (DIRS) {
+#pragma unroll
+          for (int i = 0; i < K / 4; ++i) dw[i] = 0;
+        }
 #pragma unroll
         for (int r = 0; r < K; ++r) {
           const int32_t sc = (int32_t)(int8_t)(w[r / 4] >> (8 * (r % 4)));
           const int32_t E = max(ho[r], eg[r] + e);
           const int32_t F = max(no, f + e);
           const int32_t H = max(max(sc + d, E), F);
+          if constexpr (DIRS) {
+            // the -infinity start of E and F (see above) is a tie of open and extend here, and a
+            // tie opens: the first cell of a row or a column never extends into the boundary
+            const uint32_t src = sc + d == H ? GL_SRC_M : E == H ? GL_SRC_E : GL_SRC_F;
+            const uint32_t bits = src | (eg[r] + e > ho[r] ? GL_E_EXT : 0u) |
+                                  (f + e > no ? GL_F_EXT : 0u);
+            dw[r / 4] |= bits << (8 * (r % 4));
+          }
           d = h[r];
           h[r] = H;
           ho[r] = no = H + o;
@@ -137,6 +175,11 @@ __device__ __forceinline__ GlBest gl_walk(const int8_t* prof, const Code& code, 
           f = F;
         }
         fbot = f;
+        if constexpr (DIRS) {
+          uint32_t* at = dirs + (size_t)(t0 + s) * (K / 4) * 64 + lane;
+#pragma unroll
+          for (int i = 0; i < K / 4; ++i) at[(size_t)i * 64] = dw[i];
+        }
         if constexpr (ENDS == GL_QUERY) {
           int32_t hq = h[0];
 #pragma unroll

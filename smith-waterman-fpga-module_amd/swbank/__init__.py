@@ -60,6 +60,7 @@ EXPORTS = (
     "sw_align_fshift_hits", "sw_align_fshift_hits_device",
     "sw_estimate_fshift_statistics", "sw_estimate_fshift_statistics_device",
     "sw_score_glocal", "sw_score_glocal_device",
+    "sw_align_glocal_hits", "sw_align_glocal_hits_device",
 )
 ABI_VERSION = 6
 COUNTERS = ("stream_calls", "stream_reruns", "stream_declined", "chunked_calls", "device_sorts",
@@ -301,6 +302,9 @@ def lib() -> ctypes.CDLL:
         "sw_score_fshift_device": (i32, [P, P, P, P, sz, u32, P, i32, P, P, P]),
         "sw_score_glocal": (i32, [P, P, sz, P, P, sz, i32, i32, P, P, P]),
         "sw_score_glocal_device": (i32, [P, P, P, P, sz, u32, i32, i32, P, P, P, P]),
+        "sw_align_glocal_hits": (i32, [P, P, sz, P, P, P, sz, i32, i32, P, sz, P, sz, P, P, sz, P]),
+        "sw_align_glocal_hits_device": (i32, [P, P, P, P, P, sz, u32, i32, i32, P, sz, P, sz, P, P,
+                                              u32, P]),
         "sw_align_fshift_hits": (i32, [P, P, sz, P, P, P, sz, P, i32, P, sz, P, sz, P, P, sz, P]),
         "sw_align_fshift_hits_device": (i32, [P, P, P, P, P, sz, u32, P, i32, P, sz, P, sz, P, P,
                                               u32, P]),
@@ -1037,6 +1041,52 @@ class ScoreBank:
                                           1 if both_strands else 0, _p(sc), _p(ep), _p(sd)))
         out = tuple(a[:nq * n].reshape(nq, n) for a in (sc, ep, sd))
         return tuple(a[0] for a in out) if nq == 1 else out
+
+    # alignments of global-local hits: where a pair of score_glocal starts, its CIGAR, identities
+    def align_glocal_hits(self, residues: np.ndarray, offsets: np.ndarray, lens: np.ndarray,
+                          ends: int, both_strands: bool = False, hits=None, hit_queries=None,
+                          hits_per_query: int = 0, ids: Optional[np.ndarray] = None,
+                          cigar_cap: Optional[int] = None, n_hits: Optional[int] = None) -> list:
+        """sw_align_glocal_hits: the pair list of align_set_hits over a host batch, each pair
+        aligned as score_glocal scores it under `ends`.  Alignment.score may be 0 or negative; an
+        empty Alignment (the boundary won) carries the boundary's score.  The first and the last
+        op of a CIGAR need not be M; t_start / t_end of a reverse hit are given on the forward
+        target and its CIGAR runs along the reverse strand."""
+        res, offs, ln, idv = validate_batch(residues, offsets, lens, ids)
+        hv = None if hits is None else np.ascontiguousarray(hits, dtype=np.uint64).reshape(-1)
+        hq = None if hit_queries is None else \
+            np.ascontiguousarray(hit_queries, dtype=np.uint32).reshape(-1)
+        if n_hits is None:
+            n_hits = len(hv) if hv is not None else len(hq) if hq is not None else len(ln)
+        if (hv is not None and len(hv) < n_hits) or (hq is not None and len(hq) < n_hits):
+            raise ValueError("hits / hit_queries shorter than n_hits")
+        out = np.zeros(max(n_hits, 1), dtype=ALIGNMENT_DTYPE)
+        if cigar_cap is None:  # an op consumes a query row or a target column
+            tv = hv[:n_hits] if hv is not None else np.arange(min(n_hits, len(ln)), dtype=np.uint64)
+            sel = tv[tv < len(ln)].astype(np.int64)
+            cigar_cap = int(ln[sel].astype(np.int64).sum()) + n_hits * (GLOCAL_MAX_QUERY + 1)
+        cig = np.zeros(max(cigar_cap, 1), dtype=np.uint32)
+        used = ctypes.c_size_t()
+        self._check(lib().sw_align_glocal_hits(
+            self._h, _p(res), res.size, _p(offs), _p(ln), _p(idv) if idv is not None else None,
+            len(ln), ends, 1 if both_strands else 0, _p(hq) if hq is not None else None,
+            hits_per_query, _p(hv) if hv is not None else None, n_hits, _p(out),
+            _p(cig) if cigar_cap else None, cigar_cap, ctypes.byref(used)))
+        return alignments_from(out[:n_hits], cig)
+
+    def align_glocal_hits_device(self, d_res: int, d_offs: int, d_lens: int, n: int, max_len: int,
+                                 ends: int, n_hits: int, d_out: int, both_strands: bool = False,
+                                 d_hits: int = 0, d_hit_queries: int = 0,
+                                 hits_per_query: int = 0, d_cigar: int = 0,
+                                 cigar_stride: int = 0, stream: int = 0, d_ids: int = 0):
+        """sw_align_glocal_hits_device: device pointers (ints), the pair list of
+        align_set_hits_device over the batch score_glocal_device scored under the same `ends` and
+        `both_strands`.  Async on `stream` (0: the bank's own stream; sync() before reading)."""
+        self._check(lib().sw_align_glocal_hits_device(
+            self._h, d_res or None, d_offs or None, d_lens or None, d_ids or None, n, max_len,
+            ends, 1 if both_strands else 0, d_hit_queries or None, hits_per_query,
+            d_hits or None, n_hits, d_out or None, d_cigar or None, cigar_stride,
+            stream or None))
 
     def estimate_frameshift_statistics_device(self, d_dna: int, d_offs: int, d_lens: int, n: int,
                                               max_len: int, frameshift: int, seed: int = 0,
