@@ -1201,6 +1201,87 @@ sw_status sw_align_glocal_hits(sw_bank *bank, const uint8_t *residues, size_t re
                                const uint64_t *hits, size_t n_hits, sw_alignment *out,
                                uint32_t *cigar, size_t cigar_cap, size_t *cigar_used);
 
+/* ---- non-intersecting local alignments: the next best hits of a pair (ABI 6 addition) -----------
+ * sw_align_set_hits reports the best local alignment of a pair.  These calls report up to `rounds`
+ * of them in order: the best one, then the best one that shares no matrix cell with it, and so on
+ * (Waterman and Eggert; what lalign36 prints) -- the second copy of a repeated domain, the second
+ * occurrence of a read's motif.  The pair list (hit_queries / hits_per_query / hits), the
+ * SW_ALIGN_NO_HIT sentinel slots and the sw_alignment record are sw_align_set_hits[_device]'s; a
+ * bank with one query is a set of one.  One strand, DNA and protein banks, SW_GAP_GOTOH only.
+ *
+ * The definition, for a pair with m rows and L columns, o = open + extend, e = extend.  Round r
+ * has a set U_r of used cells; U_0 is empty.
+ *     (i,j) in U_r :  H = 0, E = F = -inf            nothing passes through a used cell
+ *     otherwise    :  M = s(q_i,t_j) + H(i-1,j-1)
+ *                     E = max(H(i,j-1) + o, E(i,j-1) + e)
+ *                     F = max(H(i-1,j) + o, F(i-1,j) + e)
+ *                     H = max(0, M, E, F)
+ * with the boundaries H = 0 and E = F = -inf.
+ *   score   score_r is the largest H of round r.  score_0 is the pair's local Gotoh score, what
+ *           sw_score_batch returns; scores never increase with r.  If score_r < min_score, this
+ *           slot and every later slot of the hit is SW_ALIGN_EMPTY with score 0, every coordinate
+ *           and count 0 and no ops.
+ *   end     among the cells with H = score_r: the smallest t_end, then the smallest q_end
+ *           (sw_align_hits's rule).
+ *   path    walked back from the end cell in state H.  A cell with H = 0 ends the walk and is not
+ *           part of the path; otherwise the source M is taken first, then E (op D), then F (op
+ *           I); a gap run opens rather than extends on a tie.  The cell where the walk stops gives
+ *           q_start / t_start.  The first and the last op are M.  n_columns and n_identities are
+ *           as for sw_align_hits, and re-scoring the ops gives score_r.
+ *   used    U_{r+1} = U_r and every cell the path of round r visits in any state: the cell of
+ *           each M, D and I column.  The paths of one hit are therefore pairwise cell-disjoint.
+ *   ops     a path with more ops than its CIGAR slot gets SW_ALIGN_NO_PATH with exact coordinates;
+ *           its cells are marked all the same, so later rounds do not depend on the caller's
+ *           cigar_stride.
+ *   layout  the record of (hit h, round r) is out[h * rounds + r].  The device form puts its ops
+ *           at d_cigar + (h * rounds + r) * cigar_stride (cigar_offset says so); d_cigar == NULL
+ *           or cigar_stride == 0: coordinates only, every non-empty record gets SW_ALIGN_NO_PATH.
+ *           The host form packs the CIGARs back to back in that order into cigar[0..cigar_cap),
+ *           *cigar_used (may be NULL) = ops written; a record whose ops no longer fit gets
+ *           SW_ALIGN_NO_PATH.  A slot that names no pair has SW_ALIGN_NO_HIT in all its `rounds`
+ *           records.
+ *
+ * Limits: queries of at most SW_DISJOINT_MAX_QUERY rows, 1 <= rounds <= SW_DISJOINT_MAX_ROUNDS,
+ * min_score >= 1.  Every round walks the whole m x L matrix and keeps one direction byte per cell
+ * (bit 7 of it is the used flag), so the direction store of ONE hit, about (L + m / K) x 64K bytes
+ * with K = 4, 8 or 16 rows per lane for a longest query of at most 256, 512 or 1,024 rows, must fit
+ * SWBANK_ALIGN_MB (MiB, default 256); the hits run in chunks that fit it together, `rounds`
+ * launches per chunk.
+ *
+ * Refusals, in this order: the gap model (SW_ERR_UNSUPPORTED); the state, penalties or query not
+ * loaded (SW_ERR_STATE); a longest query over SW_DISJOINT_MAX_QUERY rows (SW_ERR_UNSUPPORTED);
+ * rounds or min_score out of range (SW_ERR_ARG); a latched hand-off fault (the device form); the
+ * multi-device bank running on its root; n_hits == 0 (SW_OK); a NULL buffer or n == 0
+ * (SW_ERR_ARG); the pair list's checks (the host form: then those of the listed targets, all
+ * SW_ERR_ARG); n_hits x rounds or n_hits x rounds x cigar_stride >= 2^32 (SW_ERR_ARG); a direction
+ * slot that alone exceeds SWBANK_ALIGN_MB (SW_ERR_UNSUPPORTED, the text names the knob): without
+ * the store there is no used set, so there is nothing exact to return.  A refused call writes
+ * nothing.  The device form sizes every slot from max_len x the longest query and reads nothing
+ * back; the host form gathers only the listed targets, checks their codes against the bank's
+ * alphabet and sizes each slot from the lengths it knows.  sw_last_kernel reports
+ * "align-disjoint i32 rounds=<r> nq=<nq> hits=<n_hits> chunks=<c>"; with sw_bank_set_timing the
+ * rounds of a chunk are bracketed as one launch. */
+#define SWBANK_HAS_DISJOINT_ALIGN 1
+#define SW_DISJOINT_MAX_QUERY 1024
+#define SW_DISJOINT_MAX_ROUNDS 64
+
+sw_status sw_align_disjoint_hits_device(sw_bank *bank, const uint8_t *d_residues,
+                                        const uint64_t *d_offsets, const uint32_t *d_lens,
+                                        const uint64_t *d_ids, size_t n, uint32_t max_len,
+                                        uint32_t rounds, int32_t min_score,
+                                        const uint32_t *d_hit_queries, size_t hits_per_query,
+                                        const uint64_t *d_hits, size_t n_hits,
+                                        sw_alignment *d_out, uint32_t *d_cigar,
+                                        uint32_t cigar_stride, void *stream);
+
+sw_status sw_align_disjoint_hits(sw_bank *bank, const uint8_t *residues, size_t residues_len,
+                                 const uint64_t *offsets, const uint32_t *lens,
+                                 const uint64_t *ids, size_t n, uint32_t rounds,
+                                 int32_t min_score, const uint32_t *hit_queries,
+                                 size_t hits_per_query, const uint64_t *hits, size_t n_hits,
+                                 sw_alignment *out, uint32_t *cigar, size_t cigar_cap,
+                                 size_t *cigar_used);
+
 /* ---- profiling(≙ the CAPI AFU's cycle counters, capi_sample_aligner/hdl-verliog/afu.v
  *      _DEBUGGING_ "calculation #N completed, runtime: C cycles") ------------------------- */
 /* When enabled, every launch is bracketed by hipEvents on the stream it runs on. */

@@ -135,6 +135,45 @@ hipError_t swk_launch_glalign_ends(const SwkGlAlign* p, hipStream_t st);
 hipError_t swk_launch_glalign_paths(const SwkGlAlign* p, const uint32_t* list, size_t h0,
                                     size_t count, const SwkAlignPlan* plan, uint64_t slot,
                                     uint32_t* dirs, hipStream_t st);
+
+/* Non-intersecting local alignments (swbank_klalign.hip): one call's arguments.  The
+ * batch and the pair list as for SwkFsAlign (any alphabet of at most 24 codes); o = open + extend,
+ * e <= 0.  The record of (hit h, round r) is out[h * rounds + r].  plan == NULL: its ops go to
+ * cigar + (h * rounds + r) * cigar_stride (cigar NULL or stride 0: no ops), and position k of a
+ * launch keeps its direction bytes in slot k of `slot` dwords.  plan != NULL, one entry per hit:
+ * the store at dirs + plan[h].dir_off (dir_cap dwords), the ops of round r at
+ * cigar + plan[h].cig_off + r * plan[h].cig_cap, at most cig_cap of them. */
+typedef struct SwkLaAlign {
+  const uint8_t* res;
+  const uint64_t* offs;
+  const uint32_t* lens;
+  const uint64_t* ids;
+  const uint64_t* hits;
+  size_t n_hits, n;
+  uint32_t max_len; /* codes of a target past it are not read */
+  const uint2* qtab;
+  const int8_t* mat;
+  const uint8_t* query;
+  uint32_t nq, qlen, alpha;
+  const uint32_t* hit_queries;
+  uint32_t hits_per_query;
+  int32_t o, e, min_score;
+  uint32_t rounds;
+  void* out; /* sw_alignment[n_hits * rounds] */
+  uint32_t* cigar;
+  uint32_t cigar_stride;
+  const SwkAlignPlan* plan;
+  uint64_t slot;
+  uint32_t* dirs;
+} SwkLaAlign;
+
+/* Dwords of direction store the whole matrix of rows x cols cells takes under the rows per lane K
+ * of queries of at most qlen rows: (cols + ceil(rows / K) - 1) steps x K bytes x 64 lanes. */
+uint64_t swk_lalign_dir_dwords(uint32_t qlen, uint32_t rows, uint32_t cols);
+/* Round `round` < rounds of hits [h0, h0 + count): walk, best cell, path, used cells, record.
+ * Round r > 0 follows round r - 1 of the same hits on the same stream. */
+hipError_t swk_launch_lalign_round(const SwkLaAlign* p, size_t h0, size_t count, uint32_t round,
+                                   hipStream_t st);
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,8 @@
 // swbank_kalign.hip.  The alignments of frameshift hits (sw_align_fshift_hits*, DESIGN.md §3.16,
 // behind them) run the same scaffolding around the kernels of swbank_kfsalign.hip, and so do the
 // alignments of global-local hits (sw_align_glocal_hits*, DESIGN.md §3.18, at the end of the file)
-// around the kernels of swbank_kglalign.hip.
+// around the kernels of swbank_kglalign.hip, and the non-intersecting local alignments
+// (sw_align_disjoint_hits*, DESIGN.md §3.19, last) around the kernel of swbank_klalign.hip.
 #include "swbank_bank.h"
 
 namespace {
@@ -1083,5 +1084,283 @@ extern "C" sw_status sw_align_glocal_hits(sw_bank* b, const uint8_t* residues, s
       cigar_cap, cigar_used, chunks);
   if (st != SW_OK) return st;
   name_glocal(b, ends, n_hits, chunks);
+  return SW_OK;
+}
+
+// ---- non-intersecting local alignments ----------------------------------------
+// Hit h (query i, target k) gets up to `rounds` records, out[h * rounds + r], from the kernel of
+// swbank_klalign.hip: one launch per round over a chunk of hits, each hit with a direction store
+// of its whole matrix that carries the used cells from round to round.  The pair list, the
+// gathering and staging of the host form and the brackets are the code above.
+namespace {
+
+// What both entries check first, in the order of the header's list.
+sw_status disjoint_opening(sw_bank* b, const char* what, uint32_t rounds, int32_t min_score) {
+  if (!b->gotoh()) return fail(b, SW_ERR_UNSUPPORTED, "%s: the Gotoh gap model only", what);
+  if (!root_of(b)->have_pen || !b->have_query)
+    return fail(b, SW_ERR_STATE, "penalties or query not loaded");
+  if (b->query.size() > SW_DISJOINT_MAX_QUERY)  // (a set: its longest query)
+    return fail(b, SW_ERR_UNSUPPORTED, "%s: a query of %zu rows (at most %d)", what,
+                b->query.size(), SW_DISJOINT_MAX_QUERY);
+  if (rounds < 1 || rounds > SW_DISJOINT_MAX_ROUNDS)
+    return fail(b, SW_ERR_ARG, "%s: rounds = %u (1 .. %d)", what, rounds, SW_DISJOINT_MAX_ROUNDS);
+  if (min_score < 1) return fail(b, SW_ERR_ARG, "%s: min_score = %d (at least 1)", what, min_score);
+  return SW_OK;
+}
+
+sw_status disjoint_sizes(sw_bank* b, const char* what, size_t n_hits, uint32_t rounds,
+                         uint64_t stride) {
+  if ((uint64_t)n_hits * rounds > 0xFFFFFFFFull)
+    return fail(b, SW_ERR_ARG, "%s: n_hits x rounds must fit 32 bits", what);
+  if (stride && (uint64_t)n_hits * rounds * stride > 0xFFFFFFFFull)
+    return fail(b, SW_ERR_ARG, "%s: n_hits x rounds x cigar_stride must fit 32 bits (cigar_offset)",
+                what);
+  return SW_OK;
+}
+
+sw_status disjoint_slot_refused(sw_bank* b, const char* what, uint64_t slot) {
+  return fail(b, SW_ERR_UNSUPPORTED,
+              "%s: the direction store of one hit (%llu MiB) exceeds SWBANK_ALIGN_MB", what,
+              (unsigned long long)((slot * 4 + ((1u << 20) - 1)) >> 20));
+}
+
+// The bank after the argument checks: prepare()d, the queries' table on the device.
+sw_status disjoint_ready(sw_bank* b, const char* what) {
+  const sw_status st = prepare(b);
+  if (st != SW_OK) return st;
+  if ((size_t)b->alpha * b->alpha != b->matrix.size() || b->alpha > SW_PROTEIN_ALPHA)
+    return fail(b, SW_ERR_UNSUPPORTED, "%s: alphabet %d too large", what, b->alpha);
+  return prepare_align(b);
+}
+
+// The launch block over a batch and a pair list already on the device.
+SwkLaAlign disjoint_block(sw_bank* b, uint32_t rounds, int32_t min_score, const uint8_t* d_res,
+                          const uint64_t* d_offs, const uint32_t* d_lens, const uint64_t* d_ids,
+                          size_t n, uint32_t max_len, const uint32_t* d_hit_queries,
+                          size_t hits_per_query, const uint64_t* d_hits, size_t n_hits,
+                          void* d_out) {
+  const size_t nq = query_count(b);
+  SwkLaAlign f{};
+  f.res = d_res;
+  f.offs = d_offs;
+  f.lens = d_lens;
+  f.ids = d_ids;
+  f.hits = d_hits;
+  f.n_hits = n_hits;
+  f.n = n;
+  f.max_len = max_len;
+  f.qtab = reinterpret_cast<const uint2*>(b->al_tab.p);
+  f.mat = reinterpret_cast<const int8_t*>(b->al_tab.p + nq * sizeof(uint2));
+  f.query = b->al_tab.p + nq * sizeof(uint2) + b->matrix.size();
+  f.nq = (uint32_t)nq;
+  f.qlen = (uint32_t)b->query.size();  // (a set: its longest query)
+  f.alpha = (uint32_t)b->alpha;
+  f.hit_queries = d_hit_queries;
+  f.hits_per_query = (uint32_t)hits_per_query;
+  f.o = b->gap_open + b->gap_extend;
+  f.e = b->gap_extend;
+  f.min_score = min_score;
+  f.rounds = rounds;
+  f.out = d_out;
+  return f;
+}
+
+// The rounds of hits [h0, h0 + count), one bracket.
+sw_status disjoint_rounds(sw_bank* b, const SwkLaAlign& f, size_t h0, size_t count,
+                          hipStream_t hs) {
+  return timed_on(b, hs, [&] {
+    for (uint32_t r = 0; r < f.rounds; ++r) {
+      const hipError_t e = swk_launch_lalign_round(&f, h0, count, r, hs);
+      if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+  });
+}
+
+void name_disjoint(sw_bank* b, uint32_t rounds, size_t hits, size_t chunks) {
+  snprintf(b->last_kernel, sizeof(b->last_kernel),
+           "align-disjoint i32 rounds=%u nq=%zu hits=%zu chunks=%zu", rounds, query_count(b), hits,
+           chunks);
+}
+
+}  // namespace
+
+extern "C" sw_status sw_align_disjoint_hits_device(sw_bank* b, const uint8_t* d_res,
+                                                   const uint64_t* d_offs, const uint32_t* d_lens,
+                                                   const uint64_t* d_ids, size_t n,
+                                                   uint32_t max_len, uint32_t rounds,
+                                                   int32_t min_score,
+                                                   const uint32_t* d_hit_queries,
+                                                   size_t hits_per_query, const uint64_t* d_hits,
+                                                   size_t n_hits, sw_alignment* d_out,
+                                                   uint32_t* d_cigar, uint32_t cigar_stride,
+                                                   void* stream) {
+  DevGuard dev_guard(b);  // on the bank's device; the caller's is restored on return (ABI 6)
+  if (!b) return SW_ERR_ARG;
+  const char* what = "sw_align_disjoint_hits_device";
+  sw_status st = disjoint_opening(b, what, rounds, min_score);
+  if (st != SW_OK) return st;
+  // a hand-off fault latched by an earlier device call is returned before anything runs
+  if (const sw_status fs = take_fault(b, 0); fs != SW_OK) return fs;
+  if (on_root(b, stream, st, [&](sw_bank* r, void* s) {
+        return sw_align_disjoint_hits_device(r, d_res, d_offs, d_lens, d_ids, n, max_len, rounds,
+                                             min_score, d_hit_queries, hits_per_query, d_hits,
+                                             n_hits, d_out, d_cigar, cigar_stride, s);
+      }))
+    return st;
+  if (n_hits == 0) return SW_OK;
+  if (!d_res || !d_offs || !d_lens || !d_out || n == 0)
+    return fail(b, SW_ERR_ARG, "null device buffer or an empty batch");
+  const Pairs pr{true, d_hit_queries, hits_per_query, d_hits, n_hits};
+  if ((st = check_pairs(b, pr, n)) != SW_OK) return st;
+  if ((st = disjoint_sizes(b, what, n_hits, rounds, d_cigar ? cigar_stride : 0)) != SW_OK)
+    return st;
+  // every slot holds the matrix of the longest query against max_len columns (a pair with no
+  // cell takes none)
+  const uint64_t slot = std::max<uint64_t>(
+      swk_lalign_dir_dwords((uint32_t)b->query.size(), (uint32_t)b->query.size(), max_len), 64);
+  const uint64_t budget = dir_budget();
+  if (slot > budget) return disjoint_slot_refused(b, what, slot);
+  if ((st = disjoint_ready(b, what)) != SW_OK) return st;
+  HIPOK(b, hipSetDevice(b->device));
+  hipStream_t hs = stream_or(b, stream);
+  const size_t per = (size_t)std::min<uint64_t>(budget / slot, n_hits);
+  HIPOK(b, b->al_dirs.reserve((size_t)(slot * per)));
+  SwkLaAlign f = disjoint_block(b, rounds, min_score, d_res, d_offs, d_lens, d_ids, n, max_len,
+                                d_hit_queries, hits_per_query, d_hits, n_hits, d_out);
+  f.cigar = d_cigar;
+  f.cigar_stride = d_cigar ? cigar_stride : 0;
+  f.slot = slot;
+  f.dirs = b->al_dirs.p;
+  HIPOK(b, hipStreamWaitEvent(hs, b->ev_ready, 0));  // the queries' codes are uploaded
+  HIPOK(b, hipStreamWaitEvent(hs, b->ev_used, 0));   // bank scratch is free
+  size_t chunks = 0;
+  for (size_t h0 = 0; st == SW_OK && h0 < n_hits; h0 += per, ++chunks)
+    st = disjoint_rounds(b, f, h0, std::min(per, n_hits - h0), hs);
+  // whatever was launched reads the table and the scratch: the next use is ordered after it
+  const hipError_t er = hipEventRecord(b->ev_used, hs);
+  if (st != SW_OK) return st;
+  HIPOK(b, er);
+  name_disjoint(b, rounds, n_hits, chunks);
+  return SW_OK;
+}
+
+extern "C" sw_status sw_align_disjoint_hits(sw_bank* b, const uint8_t* residues,
+                                            size_t residues_len, const uint64_t* offsets,
+                                            const uint32_t* lens, const uint64_t* ids, size_t n,
+                                            uint32_t rounds, int32_t min_score,
+                                            const uint32_t* hit_queries, size_t hits_per_query,
+                                            const uint64_t* hits, size_t n_hits,
+                                            sw_alignment* out, uint32_t* cigar, size_t cigar_cap,
+                                            size_t* cigar_used) {
+  DevGuard dev_guard(b);  // on the bank's device; the caller's is restored on return (ABI 6)
+  if (!b) return SW_ERR_ARG;
+  if (cigar_used) *cigar_used = 0;
+  const char* what = "sw_align_disjoint_hits";
+  sw_status st = disjoint_opening(b, what, rounds, min_score);
+  if (st != SW_OK) return st;
+  if (on_root(b, nullptr, st, [&](sw_bank* r, void*) {  // (hit lists are small)
+        return sw_align_disjoint_hits(r, residues, residues_len, offsets, lens, ids, n, rounds,
+                                      min_score, hit_queries, hits_per_query, hits, n_hits, out,
+                                      cigar, cigar_cap, cigar_used);
+      }))
+    return st;
+  if (n_hits == 0) return SW_OK;
+  if (!offsets || !lens || !out || n == 0) return fail(b, SW_ERR_ARG, "null host buffer or n = 0");
+  const Pairs pr{true, hit_queries, hits_per_query, hits, n_hits};
+  if ((st = check_pairs(b, pr, n)) != SW_OK) return st;
+  // (alpha is the bank's before prepare(): the gathering checks the listed targets' codes)
+  Gathered g;
+  if ((st = gather_hits(b, residues, residues_len, offsets, lens, n, pr, g)) != SW_OK) return st;
+  if ((st = disjoint_sizes(b, what, n_hits, rounds, 0)) != SW_OK) return st;
+  // every hit's store and ops slots from its own rows and columns; the chunks that fit the budget
+  cigar_cap = std::min<size_t>(cigar_cap, 0xFFFFFFFFu);  // (cigar_offset is 32 bits)
+  const bool with_cigar = cigar && cigar_cap;
+  const size_t nq = query_count(b);
+  const std::vector<uint8_t>* queries = nq > 1 ? b->qset.data() : &b->query;
+  const uint64_t budget = dir_budget();
+  std::vector<SwkAlignPlan> plan(n_hits);
+  std::vector<size_t> cut{0};
+  uint64_t used = 0, most = 64, ncig = 0;
+  for (size_t h = 0; h < n_hits; ++h) {
+    const uint32_t m = g.q[h] == SW_QUERY_NONE ? 0u : (uint32_t)queries[g.q[h]].size();
+    const uint32_t L = g.lens[h];
+    const uint64_t need = swk_lalign_dir_dwords((uint32_t)b->query.size(), m, L);
+    if (need > budget) return disjoint_slot_refused(b, what, need);
+    if (used + need > budget) {
+      cut.push_back(h);
+      used = 0;
+    }
+    // (runs of M alternate with gap runs, and an M run takes a row and a column)
+    const uint32_t cap = with_cigar && m && L ? 2 * std::min(m, L) - 1 : 0u;
+    plan[h] = SwkAlignPlan{used, need, ncig, cap, 0};
+    used += need;
+    most = std::max(most, used);
+    ncig += (uint64_t)cap * rounds;
+  }
+  cut.push_back(n_hits);
+  if ((st = disjoint_ready(b, what)) != SW_OK) return st;
+  HIPOK(b, hipSetDevice(b->device));
+  hipStream_t hs = b->stream;
+  const size_t n_rec = n_hits * rounds;
+  HIPOK(b, b->al_out.reserve(n_rec));  // (before the staging takes its address)
+  SwkAlign p{};  // (the staged buffers only: no launch block, no scratch rows)
+  if ((st = stage_hits(b, pr, g, p, hs, false)) != SW_OK) return st;
+  HIPOK(b, b->al_dirs.reserve((size_t)most));
+  HIPOK(b, b->al_cig.reserve((size_t)std::max<uint64_t>(ncig, 1)));
+  HIPOK(b, b->al_plan.reserve(n_hits));
+  HIPOK(b, hipMemcpyAsync(b->al_plan.p, plan.data(), n_hits * sizeof(SwkAlignPlan),
+                          hipMemcpyHostToDevice, hs));
+  // hit h is target h of the gathered batch against query al_hq[h]
+  SwkLaAlign f = disjoint_block(b, rounds, min_score, p.res, p.offs, p.lens, nullptr, n_hits,
+                                g.max_len, p.hit_queries, 0, nullptr, n_hits, b->al_out.p);
+  f.cigar = with_cigar ? b->al_cig.p : nullptr;
+  f.cigar_stride = 0;
+  f.plan = b->al_plan.p;
+  f.dirs = b->al_dirs.p;
+  size_t chunks = 0;
+  for (size_t c = 0; st == SW_OK && c + 1 < cut.size(); ++c) {
+    if (cut[c + 1] == cut[c]) continue;
+    st = disjoint_rounds(b, f, cut[c], cut[c + 1] - cut[c], hs);
+    ++chunks;
+  }
+  if (st != SW_OK) {
+    (void)hipStreamSynchronize(hs);  // (the uploads have left the host vectors)
+    (void)hipEventRecord(b->ev_used, hs);
+    return st;
+  }
+  std::vector<sw_alignment> recs(n_rec);
+  std::vector<uint32_t> ops((size_t)ncig);
+  HIPOK(b, hipMemcpyAsync(recs.data(), b->al_out.p, n_rec * sizeof(sw_alignment),
+                          hipMemcpyDeviceToHost, hs));
+  if (ncig)
+    HIPOK(b, hipMemcpyAsync(ops.data(), b->al_cig.p, ops.size() * 4, hipMemcpyDeviceToHost, hs));
+  HIPOK(b, hipStreamSynchronize(hs));
+  HIPOK(b, hipEventRecord(b->ev_used, hs));
+  // the records speak of the caller's batch; the ops back to back in record order
+  size_t at = 0;
+  for (size_t h = 0; h < n_hits; ++h) {
+    const uint64_t t = target_of(pr, h);
+    for (uint32_t r = 0; r < rounds; ++r) {
+      sw_alignment& x = recs[h * rounds + r];
+      x.cigar_offset = 0;
+      if (x.flags & SW_ALIGN_NO_HIT) continue;  // (index = id = SW_HIT_NONE)
+      x.index = t;
+      x.id = ids ? ids[t] : t;
+      if (x.flags & (SW_ALIGN_EMPTY | SW_ALIGN_NO_PATH)) continue;
+      if (x.cigar_len > cigar_cap - at) {
+        x.flags |= SW_ALIGN_NO_PATH;
+        x.cigar_len = x.n_columns = x.n_identities = 0;
+        continue;
+      }
+      std::memcpy(cigar + at, ops.data() + plan[h].cig_off + (uint64_t)r * plan[h].cig_cap,
+                  (size_t)x.cigar_len * 4);
+      x.cigar_offset = (uint32_t)at;
+      at += x.cigar_len;
+    }
+  }
+  std::memcpy(out, recs.data(), n_rec * sizeof(sw_alignment));
+  if (cigar_used) *cigar_used = at;
+  name_disjoint(b, rounds, n_hits, chunks);
   return SW_OK;
 }

@@ -9,7 +9,8 @@
  *
  * Usage: swbank -q query.fa -l library.fa [-p match,mismatch,open,extend] [-P] [-g]
  *               [-d device[,device...]] [-o out.txt] [-T] [-R scores.txt] [-b] [-A k]
- *               [-E rounds[,seed]] [-S lambda,K] [-B] [-X [-F frameshift]]
+ *               [-E rounds[,seed]] [-S lambda,K] [-B] [-X [-F frameshift]] [-G q|t|b]
+ *               [-N rounds[,min]]
  *   -p  penalties (default 5,-4,-12,-4: ScoreBank_v1_tb.sv:16-19, data/smith-waterman.py:6-10)
  *   -P  protein mode (BLOSUM62; -p gives only open,extend)      -g  Gotoh gap model
  *   -T  testbench transcript format "@     0ns: %10s score: \t%d"
@@ -68,6 +69,14 @@
  *       " [r]" follows every score, as above.  Alignments and statistics of global-local hits do
  *       not exist yet: not with -A, -E or -S; and not with -X or -F (the translated searches are
  *       local).
+ *   -N  with -A: up to `rounds` (1 to 64) non-intersecting alignments per reported hit
+ *       (sw_align_disjoint_hits; what the FASTA suite's lalign36 reports): the best local
+ *       alignment, then the best one that shares no matrix cell with it, and so on, while they
+ *       score at least `min` (default 1).  The hit's own lines are round 0 of that call (the score
+ *       and the end of -A; the path by that call's own rule); every further alignment follows as
+ *       "#r " and the summary line, then its "cigar: ..." line, r counting from 2.  The call knows
+ *       the Gotoh gap model only, so -N implies -g.  One strand, no translation: not with -B, -X,
+ *       -F or -G.
  *   -b  also print the bank's best hit ("best: >name score: S", ≙ max / vld_max) to stderr
  * FASTA: '>' starts a record (name = first token); sequence lines are concatenated; CR/LF,
  * blank lines and lower case are accepted; bytes outside the alphabet encode to N (DNA) or X
@@ -157,11 +166,14 @@ static void usage(const char *argv0) {
           "usage: %s -q query.fa -l library.fa [-p match,mismatch,open,extend] [-P] [-g]\n"
           "          [-d device[,device...]] [-o out.txt] [-T] [-R scores.txt] [-b] [-A k]\n"
           "          [-E rounds[,seed]] [-S lambda,K] [-B] [-X [-F frameshift]] [-G q|t|b]\n"
+          "          [-N rounds[,min]]\n"
           "  -X: protein query against a DNA library in six reading frames; not with -B\n"
           "  -F: with -X, follow hits across frameshifts at this penalty (0 .. -32767; implies -g);\n"
           "      not with -A, -E, -S or -B\n"
           "  -G: global-local search, end to end in the query (q), the record (t) or both (b);\n"
-          "      implies -g; not with -A, -E, -S, -X or -F\n",
+          "      implies -g; not with -A, -E, -S, -X or -F\n"
+          "  -N: with -A, up to `rounds` (1 .. 64) non-intersecting alignments per hit that score at\n"
+          "      least `min` (default 1); implies -g; not with -B, -X, -F or -G\n",
           argv0);
 }
 
@@ -177,16 +189,42 @@ static int by_score(const void *a, const void *b) {
 static const char *const kFrameTag[SW_FRAME_COUNT] = {" [+1]", " [+2]", " [+3]",
                                                       " [-1]", " [-2]", " [-3]"};
 
+/* The summary line and the CIGAR of a record that is not empty. */
+static void print_overlap(FILE *out, const sw_alignment *a, const uint32_t *cig, const char *unit) {
+  const int rev = (a->flags & SW_ALIGN_REVERSE) != 0;
+  /* the target range of a reverse hit runs high to low on the forward record */
+  const uint32_t t_from = rev ? a->t_end + 1 : a->t_start + 1;
+  const uint32_t t_to = rev ? a->t_start + 1 : a->t_end + 1;
+  if ((a->flags & ~(uint32_t)(SW_ALIGN_REVERSE | SW_ALIGN_FRAME_MASK)) == 0) {
+    const double pct = 100.0 * a->n_identities / a->n_columns;
+    fprintf(out,
+            "Smith-Waterman score: %d; %.1f%% identity (%.1f%% similar) in %u %s overlap "
+            "(%u-%u:%u-%u)\n",
+            a->score, pct, pct, a->n_columns, unit, a->q_start + 1, a->q_end + 1, t_from, t_to);
+    const size_t need = sw_cigar_string(cig + a->cigar_offset, a->cigar_len, NULL, 0);
+    char *text = malloc(need + 1);
+    if (text) {
+      sw_cigar_string(cig + a->cigar_offset, a->cigar_len, text, need + 1);
+      fprintf(out, "cigar: %s\n", text);
+      free(text);
+    }
+  } else { /* coordinates without a path (a window past SWBANK_ALIGN_MB) */
+    fprintf(out, "Smith-Waterman score: %d; no path (%u-%u:%u-%u)\ncigar: *\n", a->score,
+            a->q_start + 1, a->q_end + 1, t_from, t_to);
+  }
+}
+
 static int print_alignments(FILE *out, sw_bank *bank, const uint8_t *res, size_t total,
                             const uint64_t *offs, const uint32_t *lens, const int32_t *scores,
                             const fasta_t *lib, size_t asked, const char *unit,
                             const sw_statistics *stats, const uint8_t *strands,
-                            const uint8_t *frames) {
+                            const uint8_t *frames, uint32_t rounds, int32_t min_score) {
   const size_t k = asked < lib->n ? asked : lib->n;
   const int on_device = asked <= SW_TOP_MAX_K; /* (what -A asked for picks the path) */
   uint64_t *order = malloc((on_device ? k : lib->n) * sizeof(uint64_t));
-  sw_alignment *al = malloc(k * sizeof(sw_alignment));
-  size_t cap = k, used = 0;
+  const size_t per = rounds ? rounds : 1; /* records per hit (-N: its rounds) */
+  sw_alignment *al = malloc(k * per * sizeof(sw_alignment));
+  size_t cap = k * per, used = 0;
   if (!order || !al) {
     free(order);
     free(al);
@@ -202,10 +240,13 @@ static int print_alignments(FILE *out, sw_bank *bank, const uint8_t *res, size_t
   }
   uint32_t *cig = NULL;
   if (st == SW_OK) {
-    for (size_t i = 0; i < k; ++i) cap += 2 * (size_t)lens[order[i]]; /* ops a path can have */
+    for (size_t i = 0; i < k; ++i) cap += per * 2 * (size_t)lens[order[i]]; /* ops a path can have */
     cig = malloc(cap * sizeof(uint32_t));
     if (!cig)
       st = SW_ERR_NOMEM;
+    else if (rounds) /* -N: one query, the [1, k] layout, `rounds` records per hit */
+      st = sw_align_disjoint_hits(bank, res, total, offs, lens, NULL, lib->n, rounds, min_score,
+                                  NULL, k, order, k, al, cig, cap, &used);
     else if (frames) /* -X: one query, the [1, k] layout */
       st = sw_align_frame_hits(bank, res, total, offs, lens, NULL, lib->n, NULL, frames, NULL, k,
                                order, k, al, cig, cap, &used);
@@ -219,7 +260,7 @@ static int print_alignments(FILE *out, sw_bank *bank, const uint8_t *res, size_t
     fprintf(stderr, "swbank: %s: %s\n", sw_status_string(st), sw_last_error(bank));
   } else {
     for (size_t i = 0; i < k; ++i) {
-      const sw_alignment *a = &al[i];
+      const sw_alignment *a = &al[i * per];
       const int rev = (a->flags & SW_ALIGN_REVERSE) != 0;
       /* two strands: twice the library; six frames: six times */
       const size_t db = frames ? SW_FRAME_COUNT * lib->n : strands ? 2 * lib->n : lib->n;
@@ -235,26 +276,10 @@ static int print_alignments(FILE *out, sw_bank *bank, const uint8_t *res, size_t
         fprintf(out, "  bits: %.1f E(%zu): %.2g", bits, db, ev);
       fputc('\n', out);
       if (a->flags & SW_ALIGN_EMPTY) continue;
-      /* the target range of a reverse hit runs high to low on the forward record */
-      const uint32_t t_from = rev ? a->t_end + 1 : a->t_start + 1;
-      const uint32_t t_to = rev ? a->t_start + 1 : a->t_end + 1;
-      if ((a->flags & ~(uint32_t)(SW_ALIGN_REVERSE | SW_ALIGN_FRAME_MASK)) == 0) {
-        const double pct = 100.0 * a->n_identities / a->n_columns;
-        fprintf(out,
-                "Smith-Waterman score: %d; %.1f%% identity (%.1f%% similar) in %u %s overlap "
-                "(%u-%u:%u-%u)\n",
-                a->score, pct, pct, a->n_columns, unit, a->q_start + 1, a->q_end + 1, t_from,
-                t_to);
-        const size_t need = sw_cigar_string(cig + a->cigar_offset, a->cigar_len, NULL, 0);
-        char *text = malloc(need + 1);
-        if (text) {
-          sw_cigar_string(cig + a->cigar_offset, a->cigar_len, text, need + 1);
-          fprintf(out, "cigar: %s\n", text);
-          free(text);
-        }
-      } else { /* coordinates without a path (a window past SWBANK_ALIGN_MB) */
-        fprintf(out, "Smith-Waterman score: %d; no path (%u-%u:%u-%u)\ncigar: *\n", a->score,
-                a->q_start + 1, a->q_end + 1, t_from, t_to);
+      print_overlap(out, a, cig, unit);
+      for (size_t r = 1; r < per && !(a[r].flags & SW_ALIGN_EMPTY); ++r) { /* -N: the next best */
+        fprintf(out, "#%zu ", r + 1);
+        print_overlap(out, a + r, cig, unit);
       }
     }
   }
@@ -268,13 +293,13 @@ int main(int argc, char **argv) {
   const char *qpath = NULL, *lpath = NULL, *opath = NULL, *pen = NULL, *rpath = NULL;
   int protein = 0, gotoh = 0, device = -1, transcript = 0, best = 0, both = 0, xlate = 0, opt;
   int ndev = 0, devs[SW_MAX_DEVICES], fshift = 0, glocal = 0;
-  long nalign = 0, fs = 0;
+  long nalign = 0, fs = 0, nrounds = 0, nmin = 1;
   int have_stats = 0; /* 1: -S (given), 2: -E (estimated) */
   unsigned long stat_rounds = 0;
   unsigned long long stat_seed = 0;
   sw_statistics stats;
   memset(&stats, 0, sizeof(stats));
-  while ((opt = getopt(argc, argv, "q:l:p:Pgd:o:TR:bA:E:S:BXF:G:h")) != -1) {
+  while ((opt = getopt(argc, argv, "q:l:p:Pgd:o:TR:bA:E:S:BXF:G:N:h")) != -1) {
     switch (opt) {
       case 'q': qpath = optarg; break;
       case 'l': lpath = optarg; break;
@@ -318,6 +343,23 @@ int main(int argc, char **argv) {
         }
         gotoh = 1;
         break;
+      case 'N': {
+        char *end;
+        nrounds = strtol(optarg, &end, 10);
+        if (end != optarg && *end == ',') {
+          char *p = end + 1;
+          nmin = strtol(p, &end, 10);
+          if (end == p) nmin = 0;
+        }
+        if (end == optarg || *end || nrounds < 1 || nrounds > SW_DISJOINT_MAX_ROUNDS || nmin < 1 ||
+            nmin > INT32_MAX) {
+          fprintf(stderr, "-N takes rounds[,min]: 1 to %d alignments per hit, min at least 1\n",
+                  SW_DISJOINT_MAX_ROUNDS);
+          return usage(argv[0]), 1;
+        }
+        gotoh = 1;
+        break;
+      }
       case 'A': {
         char *end;
         nalign = strtol(optarg, &end, 10);
@@ -373,6 +415,18 @@ int main(int argc, char **argv) {
         : nalign > 0    ? "-G: alignments of global-local hits do not exist yet: not with -A"
         : have_stats    ? "-G: statistics of global-local scores do not exist yet: not with -E or -S"
                         : NULL;
+    if (why) {
+      fprintf(stderr, "%s\n", why);
+      usage(argv[0]);
+      return 1;
+    }
+  }
+  if (nrounds) {
+    const char *why =
+        nalign <= 0 ? "-N lists further alignments of the hits of -A: it needs -A"
+        : both || xlate || fshift || glocal
+            ? "-N aligns one strand locally, untranslated: not with -B, -X, -F or -G"
+            : NULL;
     if (why) {
       fprintf(stderr, "%s\n", why);
       usage(argv[0]);
@@ -516,7 +570,8 @@ int main(int argc, char **argv) {
             (unsigned long long)stats.n_samples);
   if (nalign > 0 && lib.n) {
     int rc = print_alignments(out, bank, res, total, offs, lens, scores, &lib, (size_t)nalign,
-                              protein ? "aa" : "nt", have_stats ? &stats : NULL, strands, frames);
+                              protein ? "aa" : "nt", have_stats ? &stats : NULL, strands, frames,
+                              (uint32_t)nrounds, (int32_t)nmin);
     if (rc) {
       if (opath) fclose(out);
       sw_bank_destroy(bank);
