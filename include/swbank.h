@@ -99,7 +99,10 @@ extern "C" {
  *        (test SWBANK_HAS_GLOCAL) the global-local search -- sw_score_glocal[_device],
  *        SW_ENDS_QUERY / _TARGET / _BOTH, SW_END_NONE, SW_GLOCAL_MAX_QUERY; (test
  *        SWBANK_HAS_GLOCAL_ALIGN) alignments of global-local hits --
- *        sw_align_glocal_hits[_device]. */
+ *        sw_align_glocal_hits[_device]; (test SWBANK_HAS_DISJOINT_ALIGN) the next best
+ *        alignments of a pair -- sw_align_disjoint_hits[_device], SW_DISJOINT_MAX_QUERY /
+ *        _MAX_ROUNDS; (test SWBANK_HAS_DISJOINT_FRAMES) the same over the six reading frames of
+ *        a translated hit -- sw_align_disjoint_frame_hits[_device]. */
 #define SWBANK_ABI_VERSION 6
 #define SWBANK_HAS_ALIGN 1
 #define SWBANK_HAS_TOPK 1
@@ -1281,6 +1284,75 @@ sw_status sw_align_disjoint_hits(sw_bank *bank, const uint8_t *residues, size_t 
                                  size_t hits_per_query, const uint64_t *hits, size_t n_hits,
                                  sw_alignment *out, uint32_t *cigar, size_t cigar_cap,
                                  size_t *cigar_used);
+
+/* ---- non-intersecting alignments over reading frames: every exon of a hit (ABI 6 addition) ------
+ * sw_align_frame_hits aligns a hit of the translated search on its one best frame, and
+ * sw_align_disjoint_hits walks one matrix on one strand.  A protein's exons in a contig lie in
+ * different reading frames and on either strand; these calls report up to `rounds` alignments of
+ * a hit over all six frames, best first, in one call that chains behind sw_score_frames_device
+ * and sw_top_hits_device on one stream.  Protein banks, SW_GAP_GOTOH only.  The batch holds DNA
+ * codes as for sw_score_frames; codon_table is as there (NULL: the standard code).
+ *
+ * The definition.  For a hit (query i, target k of L codes) let S_f, f = 0..5, be the records
+ * sw_align_disjoint_hits returns for the pair (query i, sw_translate_codes(target k, frame f)) at
+ * the same `rounds` and min_score: non-increasing in score, ending at its first empty record.  The
+ * call returns the first `rounds` records of the merge of S_0 .. S_5: at each step the head with
+ * the largest score, a tie to the lowest frame; within a frame S_f's order.  When every head is
+ * empty, that slot and every later slot of the hit is SW_ALIGN_EMPTY: score 0, all coordinates
+ * and counts 0, no ops, no frame bits.  A record taken from frame f is S_f's record with, as
+ * sw_align_frame_hits reports them,
+ *   index and id naming the DNA target,
+ *   flags |= (f % 3) << SW_ALIGN_FRAME_SHIFT, and |= SW_ALIGN_REVERSE for f >= 3,
+ *   t_start / t_end in nucleotides on the forward target,
+ * while q_*, the counts and the CIGAR stay in amino-acid columns.  A record with SW_ALIGN_NO_PATH
+ * had more ops than its slot; its cells are used all the same.  It follows that record 0 has the
+ * score and the frame of sw_score_frames (both break ties to the lowest frame), that scores never
+ * increase along the records of a hit, and that two records of a hit in the same frame share no
+ * cell.
+ *
+ * The layout (record (h, r) at out[h * rounds + r]), the pair list, the SW_ALIGN_NO_HIT sentinel
+ * slots and the CIGAR placement of both forms are sw_align_disjoint_hits[_device]'s, and so are
+ * SW_DISJOINT_MAX_QUERY, SW_DISJOINT_MAX_ROUNDS and min_score >= 1.  Round 0 walks the six
+ * matrices at once and every later round only the matrix the previous record came from: 6 +
+ * (rounds - 1) walks per hit.  The direction store of ONE hit, the sum over the frames of the
+ * disjoint call's store for that frame's codons, must fit SWBANK_ALIGN_MB; the hits run in chunks
+ * that fit it together, `rounds` launches per chunk.  The device form sizes every hit at six
+ * stores of the longest query against max_len / 3 codons and reads nothing back; the host form
+ * gathers only the listed targets, checks that their codes are DNA codes (< SW_DNA_ALPHA) and
+ * sizes each hit from the lengths it knows, a CIGAR slot per round from the longest frame's
+ * codons.
+ *
+ * Refusals, in this order: a DNA bank (SW_ERR_UNSUPPORTED); the gap model (SW_ERR_UNSUPPORTED);
+ * the state, penalties or query not loaded (SW_ERR_STATE); a longest query over
+ * SW_DISJOINT_MAX_QUERY rows (SW_ERR_UNSUPPORTED); rounds or min_score out of range, then a codon
+ * table entry >= SW_PROTEIN_ALPHA (SW_ERR_ARG); a latched hand-off fault (the device form); the
+ * multi-device bank running on its root; n_hits == 0 (SW_OK); a NULL buffer or n == 0
+ * (SW_ERR_ARG); the pair list's checks (the host form: then those of the listed targets, all
+ * SW_ERR_ARG); n_hits x rounds or n_hits x rounds x cigar_stride >= 2^32 (SW_ERR_ARG); a hit
+ * whose store alone exceeds SWBANK_ALIGN_MB (SW_ERR_UNSUPPORTED, the text names the knob).  A
+ * refused call writes nothing.  sw_last_kernel reports
+ * "align-disjoint-frames i32 rounds=<r> nq=<nq> hits=<n_hits> chunks=<c>"; with
+ * sw_bank_set_timing the rounds of a chunk are bracketed as one launch. */
+#define SWBANK_HAS_DISJOINT_FRAMES 1
+
+sw_status sw_align_disjoint_frame_hits_device(sw_bank *bank, const uint8_t *d_residues,
+                                              const uint64_t *d_offsets, const uint32_t *d_lens,
+                                              const uint64_t *d_ids, size_t n, uint32_t max_len,
+                                              const uint8_t *codon_table, uint32_t rounds,
+                                              int32_t min_score, const uint32_t *d_hit_queries,
+                                              size_t hits_per_query, const uint64_t *d_hits,
+                                              size_t n_hits, sw_alignment *d_out,
+                                              uint32_t *d_cigar, uint32_t cigar_stride,
+                                              void *stream);
+
+sw_status sw_align_disjoint_frame_hits(sw_bank *bank, const uint8_t *residues,
+                                       size_t residues_len, const uint64_t *offsets,
+                                       const uint32_t *lens, const uint64_t *ids, size_t n,
+                                       const uint8_t *codon_table, uint32_t rounds,
+                                       int32_t min_score, const uint32_t *hit_queries,
+                                       size_t hits_per_query, const uint64_t *hits, size_t n_hits,
+                                       sw_alignment *out, uint32_t *cigar, size_t cigar_cap,
+                                       size_t *cigar_used);
 
 /* ---- profiling(≙ the CAPI AFU's cycle counters, capi_sample_aligner/hdl-verliog/afu.v
  *      _DEBUGGING_ "calculation #N completed, runtime: C cycles") ------------------------- */

@@ -174,6 +174,27 @@ uint64_t swk_lalign_dir_dwords(uint32_t qlen, uint32_t rows, uint32_t cols);
  * Round r > 0 follows round r - 1 of the same hits on the same stream. */
 hipError_t swk_launch_lalign_round(const SwkLaAlign* p, size_t h0, size_t count, uint32_t round,
                                    hipStream_t st);
+
+/* Non-intersecting alignments over the six reading frames of a hit (swbank_klaframes.hip, DESIGN
+ * 3.20): one call's arguments.  `a` as for swk_launch_lalign_round, but the batch holds DNA codes
+ * and alpha is the protein matrix's; a hit's direction store (a slot, or plan[h].dir_cap dwords)
+ * holds the stores of its six frames back to back, frame f's of
+ * swk_lalign_dir_dwords(qlen, m, codons of frame f) dwords.  table: 64 protein codes.  state:
+ * SWK_LAFRAMES_STATE dwords per position of a launch, written by round 0 and carried through the
+ * rounds of those positions: {score, column, row} of each frame's best remaining cell, then the
+ * frame of the last record. */
+#define SWK_LAFRAMES_STATE 20
+typedef struct SwkLaFrames {
+  SwkLaAlign a;
+  uint8_t table[64];
+  int32_t* state;
+} SwkLaFrames;
+
+/* Dwords of direction store the six frames of a target of `len` codes take against `rows` rows. */
+uint64_t swk_laframes_dir_dwords(uint32_t qlen, uint32_t rows, uint32_t len);
+/* Round `round` < rounds of hits [h0, h0 + count), as swk_launch_lalign_round. */
+hipError_t swk_launch_laframes_round(const SwkLaFrames* p, size_t h0, size_t count, uint32_t round,
+                                     hipStream_t st);
 #ifdef __cplusplus
 }
 #endif

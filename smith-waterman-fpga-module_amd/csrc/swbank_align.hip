@@ -7,7 +7,9 @@
 // behind them) run the same scaffolding around the kernels of swbank_kfsalign.hip, and so do the
 // alignments of global-local hits (sw_align_glocal_hits*, DESIGN.md §3.18, at the end of the file)
 // around the kernels of swbank_kglalign.hip, and the non-intersecting local alignments
-// (sw_align_disjoint_hits*, DESIGN.md §3.19, last) around the kernel of swbank_klalign.hip.
+// (sw_align_disjoint_hits*) around the kernel of swbank_klalign.hip, and those
+// over the six reading frames of a translated hit (sw_align_disjoint_frame_hits*, DESIGN.md §3.20,
+// last) around the kernels of swbank_klaframes.hip.
 #include "swbank_bank.h"
 
 namespace {
@@ -1177,6 +1179,48 @@ sw_status disjoint_rounds(sw_bank* b, const SwkLaAlign& f, size_t h0, size_t cou
   });
 }
 
+// The end of a host form: the records and the planned ops slots back from the device (al_out,
+// al_cig; ncig ops slots in all); the records speak of the caller's batch, the ops are packed
+// back to back in record order into cigar[0, cigar_cap).
+sw_status disjoint_collect(sw_bank* b, const Pairs& pr, const uint64_t* ids,
+                           const std::vector<SwkAlignPlan>& plan, uint32_t rounds, uint64_t ncig,
+                           hipStream_t hs, sw_alignment* out, uint32_t* cigar, size_t cigar_cap,
+                           size_t* cigar_used) {
+  const size_t n_hits = pr.n_hits, n_rec = n_hits * rounds;
+  std::vector<sw_alignment> recs(n_rec);
+  std::vector<uint32_t> ops((size_t)ncig);
+  HIPOK(b, hipMemcpyAsync(recs.data(), b->al_out.p, n_rec * sizeof(sw_alignment),
+                          hipMemcpyDeviceToHost, hs));
+  if (ncig)
+    HIPOK(b, hipMemcpyAsync(ops.data(), b->al_cig.p, ops.size() * 4, hipMemcpyDeviceToHost, hs));
+  HIPOK(b, hipStreamSynchronize(hs));
+  HIPOK(b, hipEventRecord(b->ev_used, hs));
+  size_t at = 0;
+  for (size_t h = 0; h < n_hits; ++h) {
+    const uint64_t t = target_of(pr, h);
+    for (uint32_t r = 0; r < rounds; ++r) {
+      sw_alignment& x = recs[h * rounds + r];
+      x.cigar_offset = 0;
+      if (x.flags & SW_ALIGN_NO_HIT) continue;  // (index = id = SW_HIT_NONE)
+      x.index = t;
+      x.id = ids ? ids[t] : t;
+      if (x.flags & (SW_ALIGN_EMPTY | SW_ALIGN_NO_PATH)) continue;
+      if (x.cigar_len > cigar_cap - at) {
+        x.flags |= SW_ALIGN_NO_PATH;
+        x.cigar_len = x.n_columns = x.n_identities = 0;
+        continue;
+      }
+      std::memcpy(cigar + at, ops.data() + plan[h].cig_off + (uint64_t)r * plan[h].cig_cap,
+                  (size_t)x.cigar_len * 4);
+      x.cigar_offset = (uint32_t)at;
+      at += x.cigar_len;
+    }
+  }
+  std::memcpy(out, recs.data(), n_rec * sizeof(sw_alignment));
+  if (cigar_used) *cigar_used = at;
+  return SW_OK;
+}
+
 void name_disjoint(sw_bank* b, uint32_t rounds, size_t hits, size_t chunks) {
   snprintf(b->last_kernel, sizeof(b->last_kernel),
            "align-disjoint i32 rounds=%u nq=%zu hits=%zu chunks=%zu", rounds, query_count(b), hits,
@@ -1329,38 +1373,210 @@ extern "C" sw_status sw_align_disjoint_hits(sw_bank* b, const uint8_t* residues,
     (void)hipEventRecord(b->ev_used, hs);
     return st;
   }
-  std::vector<sw_alignment> recs(n_rec);
-  std::vector<uint32_t> ops((size_t)ncig);
-  HIPOK(b, hipMemcpyAsync(recs.data(), b->al_out.p, n_rec * sizeof(sw_alignment),
-                          hipMemcpyDeviceToHost, hs));
-  if (ncig)
-    HIPOK(b, hipMemcpyAsync(ops.data(), b->al_cig.p, ops.size() * 4, hipMemcpyDeviceToHost, hs));
-  HIPOK(b, hipStreamSynchronize(hs));
-  HIPOK(b, hipEventRecord(b->ev_used, hs));
-  // the records speak of the caller's batch; the ops back to back in record order
-  size_t at = 0;
-  for (size_t h = 0; h < n_hits; ++h) {
-    const uint64_t t = target_of(pr, h);
-    for (uint32_t r = 0; r < rounds; ++r) {
-      sw_alignment& x = recs[h * rounds + r];
-      x.cigar_offset = 0;
-      if (x.flags & SW_ALIGN_NO_HIT) continue;  // (index = id = SW_HIT_NONE)
-      x.index = t;
-      x.id = ids ? ids[t] : t;
-      if (x.flags & (SW_ALIGN_EMPTY | SW_ALIGN_NO_PATH)) continue;
-      if (x.cigar_len > cigar_cap - at) {
-        x.flags |= SW_ALIGN_NO_PATH;
-        x.cigar_len = x.n_columns = x.n_identities = 0;
-        continue;
-      }
-      std::memcpy(cigar + at, ops.data() + plan[h].cig_off + (uint64_t)r * plan[h].cig_cap,
-                  (size_t)x.cigar_len * 4);
-      x.cigar_offset = (uint32_t)at;
-      at += x.cigar_len;
-    }
-  }
-  std::memcpy(out, recs.data(), n_rec * sizeof(sw_alignment));
-  if (cigar_used) *cigar_used = at;
+  if ((st = disjoint_collect(b, pr, ids, plan, rounds, ncig, hs, out, cigar, cigar_cap,
+                             cigar_used)) != SW_OK)
+    return st;
   name_disjoint(b, rounds, n_hits, chunks);
+  return SW_OK;
+}
+
+// ---- non-intersecting alignments over the six reading frames -------------------
+// Hit h (protein query i, DNA target k) gets up to `rounds` records, out[h * rounds + r], from the
+// kernels of swbank_klaframes.hip: the merge, best first, of the non-intersecting alignments of
+// the query with each of the target's six translations.  A hit's direction store holds its six
+// matrices back to back; its six pending candidates live in al_state.  Everything else is the
+// code of the disjoint entries above.
+namespace {
+
+// What both entries check first, in the order of the header's list.
+sw_status disjoint_frames_opening(sw_bank* b, const char* what, const uint8_t* codon_table,
+                                  uint32_t rounds, int32_t min_score, uint8_t tab[64]) {
+  if (b->cfg.alphabet != SW_ALPHABET_PROTEIN)
+    return fail(b, SW_ERR_UNSUPPORTED, "%s: protein banks only", what);
+  const sw_status st = disjoint_opening(b, what, rounds, min_score);
+  if (st != SW_OK) return st;
+  if (!swbank_codon_table(codon_table, tab))
+    return fail(b, SW_ERR_ARG, "a codon table entry is no protein code (>= %d)", SW_PROTEIN_ALPHA);
+  return SW_OK;
+}
+
+// The rounds of hits [h0, h0 + count), one bracket.
+sw_status disjoint_frames_rounds(sw_bank* b, const SwkLaFrames& f, size_t h0, size_t count,
+                                 hipStream_t hs) {
+  return timed_on(b, hs, [&] {
+    for (uint32_t r = 0; r < f.a.rounds; ++r) {
+      const hipError_t e = swk_launch_laframes_round(&f, h0, count, r, hs);
+      if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+  });
+}
+
+void name_disjoint_frames(sw_bank* b, uint32_t rounds, size_t hits, size_t chunks) {
+  snprintf(b->last_kernel, sizeof(b->last_kernel),
+           "align-disjoint-frames i32 rounds=%u nq=%zu hits=%zu chunks=%zu", rounds,
+           query_count(b), hits, chunks);
+}
+
+}  // namespace
+
+extern "C" sw_status sw_align_disjoint_frame_hits_device(
+    sw_bank* b, const uint8_t* d_res, const uint64_t* d_offs, const uint32_t* d_lens,
+    const uint64_t* d_ids, size_t n, uint32_t max_len, const uint8_t* codon_table, uint32_t rounds,
+    int32_t min_score, const uint32_t* d_hit_queries, size_t hits_per_query,
+    const uint64_t* d_hits, size_t n_hits, sw_alignment* d_out, uint32_t* d_cigar,
+    uint32_t cigar_stride, void* stream) {
+  DevGuard dev_guard(b);  // on the bank's device; the caller's is restored on return (ABI 6)
+  if (!b) return SW_ERR_ARG;
+  const char* what = "sw_align_disjoint_frame_hits_device";
+  SwkLaFrames f{};
+  sw_status st = disjoint_frames_opening(b, what, codon_table, rounds, min_score, f.table);
+  if (st != SW_OK) return st;
+  // a hand-off fault latched by an earlier device call is returned before anything runs
+  if (const sw_status fs = take_fault(b, 0); fs != SW_OK) return fs;
+  if (on_root(b, stream, st, [&](sw_bank* r, void* s) {
+        return sw_align_disjoint_frame_hits_device(r, d_res, d_offs, d_lens, d_ids, n, max_len,
+                                                   codon_table, rounds, min_score, d_hit_queries,
+                                                   hits_per_query, d_hits, n_hits, d_out, d_cigar,
+                                                   cigar_stride, s);
+      }))
+    return st;
+  if (n_hits == 0) return SW_OK;
+  if (!d_res || !d_offs || !d_lens || !d_out || n == 0)
+    return fail(b, SW_ERR_ARG, "null device buffer or an empty batch");
+  const Pairs pr{true, d_hit_queries, hits_per_query, d_hits, n_hits};
+  if ((st = check_pairs(b, pr, n)) != SW_OK) return st;
+  if ((st = disjoint_sizes(b, what, n_hits, rounds, d_cigar ? cigar_stride : 0)) != SW_OK)
+    return st;
+  // every slot holds six matrices of the longest query against the codons of max_len codes
+  const uint64_t slot = std::max<uint64_t>(
+      6 * swk_lalign_dir_dwords((uint32_t)b->query.size(), (uint32_t)b->query.size(), max_len / 3),
+      64);
+  const uint64_t budget = dir_budget();
+  if (slot > budget) return disjoint_slot_refused(b, what, slot);
+  if ((st = disjoint_ready(b, what)) != SW_OK) return st;
+  HIPOK(b, hipSetDevice(b->device));
+  hipStream_t hs = stream_or(b, stream);
+  const size_t per = (size_t)std::min<uint64_t>(budget / slot, n_hits);
+  HIPOK(b, b->al_dirs.reserve((size_t)(slot * per)));
+  HIPOK(b, b->al_state.reserve(per * SWK_LAFRAMES_STATE));
+  f.a = disjoint_block(b, rounds, min_score, d_res, d_offs, d_lens, d_ids, n, max_len,
+                       d_hit_queries, hits_per_query, d_hits, n_hits, d_out);
+  f.a.cigar = d_cigar;
+  f.a.cigar_stride = d_cigar ? cigar_stride : 0;
+  f.a.slot = slot;
+  f.a.dirs = b->al_dirs.p;
+  f.state = b->al_state.p;
+  HIPOK(b, hipStreamWaitEvent(hs, b->ev_ready, 0));  // the queries' codes are uploaded
+  HIPOK(b, hipStreamWaitEvent(hs, b->ev_used, 0));   // bank scratch is free
+  size_t chunks = 0;
+  for (size_t h0 = 0; st == SW_OK && h0 < n_hits; h0 += per, ++chunks)
+    st = disjoint_frames_rounds(b, f, h0, std::min(per, n_hits - h0), hs);
+  // whatever was launched reads the table and the scratch: the next use is ordered after it
+  const hipError_t er = hipEventRecord(b->ev_used, hs);
+  if (st != SW_OK) return st;
+  HIPOK(b, er);
+  name_disjoint_frames(b, rounds, n_hits, chunks);
+  return SW_OK;
+}
+
+extern "C" sw_status sw_align_disjoint_frame_hits(
+    sw_bank* b, const uint8_t* residues, size_t residues_len, const uint64_t* offsets,
+    const uint32_t* lens, const uint64_t* ids, size_t n, const uint8_t* codon_table,
+    uint32_t rounds, int32_t min_score, const uint32_t* hit_queries, size_t hits_per_query,
+    const uint64_t* hits, size_t n_hits, sw_alignment* out, uint32_t* cigar, size_t cigar_cap,
+    size_t* cigar_used) {
+  DevGuard dev_guard(b);  // on the bank's device; the caller's is restored on return (ABI 6)
+  if (!b) return SW_ERR_ARG;
+  if (cigar_used) *cigar_used = 0;
+  const char* what = "sw_align_disjoint_frame_hits";
+  SwkLaFrames f{};
+  sw_status st = disjoint_frames_opening(b, what, codon_table, rounds, min_score, f.table);
+  if (st != SW_OK) return st;
+  if (on_root(b, nullptr, st, [&](sw_bank* r, void*) {  // (hit lists are small)
+        return sw_align_disjoint_frame_hits(r, residues, residues_len, offsets, lens, ids, n,
+                                            codon_table, rounds, min_score, hit_queries,
+                                            hits_per_query, hits, n_hits, out, cigar, cigar_cap,
+                                            cigar_used);
+      }))
+    return st;
+  if (n_hits == 0) return SW_OK;
+  if (!offsets || !lens || !out || n == 0) return fail(b, SW_ERR_ARG, "null host buffer or n = 0");
+  const Pairs pr{true, hit_queries, hits_per_query, hits, n_hits};
+  if ((st = check_pairs(b, pr, n)) != SW_OK) return st;
+  Gathered g;
+  if ((st = gather_hits(b, residues, residues_len, offsets, lens, n, pr, g)) != SW_OK) return st;
+  for (size_t h = 0; h < n_hits; ++h)  // (the gathering knows the bank's protein alphabet)
+    for (uint32_t i = 0; i < g.lens[h]; ++i)
+      if (g.res[g.offs[h] + i] >= SW_DNA_ALPHA)
+        return fail(b, SW_ERR_ARG, "target %llu code %u at %u is no DNA code",
+                    (unsigned long long)target_of(pr, h), g.res[g.offs[h] + i], i);
+  if ((st = disjoint_sizes(b, what, n_hits, rounds, 0)) != SW_OK) return st;
+  // every hit's six stores from its own rows and codons, its ops slots from the longest frame's
+  // codons; the chunks that fit the budget
+  cigar_cap = std::min<size_t>(cigar_cap, 0xFFFFFFFFu);  // (cigar_offset is 32 bits)
+  const bool with_cigar = cigar && cigar_cap;
+  const size_t nq = query_count(b);
+  const std::vector<uint8_t>* queries = nq > 1 ? b->qset.data() : &b->query;
+  const uint64_t budget = dir_budget();
+  std::vector<SwkAlignPlan> plan(n_hits);
+  std::vector<size_t> cut{0};
+  uint64_t used = 0, most = 64, ncig = 0;
+  size_t widest = 1;
+  for (size_t h = 0; h < n_hits; ++h) {
+    const uint32_t m = g.q[h] == SW_QUERY_NONE ? 0u : (uint32_t)queries[g.q[h]].size();
+    const uint32_t L = g.lens[h];
+    const uint64_t need = swk_laframes_dir_dwords((uint32_t)b->query.size(), m, L);
+    if (need > budget) return disjoint_slot_refused(b, what, need);
+    if (used + need > budget) {
+      widest = std::max(widest, h - cut.back());
+      cut.push_back(h);
+      used = 0;
+    }
+    // (runs of M alternate with gap runs, and an M run takes a row and a column)
+    const uint32_t cap = with_cigar && m && L / 3 ? 2 * std::min(m, L / 3) - 1 : 0u;
+    plan[h] = SwkAlignPlan{used, need, ncig, cap, 0};
+    used += need;
+    most = std::max(most, used);
+    ncig += (uint64_t)cap * rounds;
+  }
+  widest = std::max(widest, n_hits - cut.back());
+  cut.push_back(n_hits);
+  if ((st = disjoint_ready(b, what)) != SW_OK) return st;
+  HIPOK(b, hipSetDevice(b->device));
+  hipStream_t hs = b->stream;
+  const size_t n_rec = n_hits * rounds;
+  HIPOK(b, b->al_out.reserve(n_rec));  // (before the staging takes its address)
+  SwkAlign p{};  // (the staged buffers only: no launch block, no scratch rows)
+  if ((st = stage_hits(b, pr, g, p, hs, false)) != SW_OK) return st;
+  HIPOK(b, b->al_dirs.reserve((size_t)most));
+  HIPOK(b, b->al_state.reserve(widest * SWK_LAFRAMES_STATE));
+  HIPOK(b, b->al_cig.reserve((size_t)std::max<uint64_t>(ncig, 1)));
+  HIPOK(b, b->al_plan.reserve(n_hits));
+  HIPOK(b, hipMemcpyAsync(b->al_plan.p, plan.data(), n_hits * sizeof(SwkAlignPlan),
+                          hipMemcpyHostToDevice, hs));
+  // hit h is target h of the gathered batch against query al_hq[h]
+  f.a = disjoint_block(b, rounds, min_score, p.res, p.offs, p.lens, nullptr, n_hits, g.max_len,
+                       p.hit_queries, 0, nullptr, n_hits, b->al_out.p);
+  f.a.cigar = with_cigar ? b->al_cig.p : nullptr;
+  f.a.cigar_stride = 0;
+  f.a.plan = b->al_plan.p;
+  f.a.dirs = b->al_dirs.p;
+  f.state = b->al_state.p;
+  size_t chunks = 0;
+  for (size_t c = 0; st == SW_OK && c + 1 < cut.size(); ++c) {
+    if (cut[c + 1] == cut[c]) continue;
+    st = disjoint_frames_rounds(b, f, cut[c], cut[c + 1] - cut[c], hs);
+    ++chunks;
+  }
+  if (st != SW_OK) {
+    (void)hipStreamSynchronize(hs);  // (the uploads have left the host vectors)
+    (void)hipEventRecord(b->ev_used, hs);
+    return st;
+  }
+  if ((st = disjoint_collect(b, pr, ids, plan, rounds, ncig, hs, out, cigar, cigar_cap,
+                             cigar_used)) != SW_OK)
+    return st;
+  name_disjoint_frames(b, rounds, n_hits, chunks);
   return SW_OK;
 }

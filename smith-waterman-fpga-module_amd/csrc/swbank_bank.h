@@ -546,6 +546,9 @@ struct sw_bank {
   DevBuf<uint64_t> al_offs;
   DevBuf<sw_alignment> al_out;
   DevBuf<SwkAlignPlan> al_plan;
+  // the pending candidates of sw_align_disjoint_frame_hits*, SWK_LAFRAMES_STATE dwords per hit of
+  // a chunk, under ev_used like al_dirs
+  DevBuf<int32_t> al_state;
   // the k best hits (swbank_top.hip): the select's per-row state and key slots; the host call's
   // scores and results on the device; ev_top follows the last call's use of the four, on
   // whichever stream it ran, and the next call's stream waits for it.  The column best

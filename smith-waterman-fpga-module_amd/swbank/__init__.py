@@ -62,6 +62,7 @@ EXPORTS = (
     "sw_score_glocal", "sw_score_glocal_device",
     "sw_align_glocal_hits", "sw_align_glocal_hits_device",
     "sw_align_disjoint_hits", "sw_align_disjoint_hits_device",
+    "sw_align_disjoint_frame_hits", "sw_align_disjoint_frame_hits_device",
 )
 ABI_VERSION = 6
 COUNTERS = ("stream_calls", "stream_reruns", "stream_declined", "chunked_calls", "device_sorts",
@@ -312,6 +313,10 @@ def lib() -> ctypes.CDLL:
                                          P]),
         "sw_align_disjoint_hits_device": (i32, [P, P, P, P, P, sz, u32, u32, i32, P, sz, P, sz, P,
                                                 P, u32, P]),
+        "sw_align_disjoint_frame_hits": (i32, [P, P, sz, P, P, P, sz, P, u32, i32, P, sz, P, sz, P,
+                                               P, sz, P]),
+        "sw_align_disjoint_frame_hits_device": (i32, [P, P, P, P, P, sz, u32, P, u32, i32, P, sz,
+                                                      P, sz, P, P, u32, P]),
         "sw_align_fshift_hits": (i32, [P, P, sz, P, P, P, sz, P, i32, P, sz, P, sz, P, P, sz, P]),
         "sw_align_fshift_hits_device": (i32, [P, P, P, P, P, sz, u32, P, i32, P, sz, P, sz, P, P,
                                               u32, P]),
@@ -1143,6 +1148,63 @@ class ScoreBank:
             self._h, d_res or None, d_offs or None, d_lens or None, d_ids or None, n, max_len,
             rounds, min_score, d_hit_queries or None, hits_per_query, d_hits or None, n_hits,
             d_out or None, d_cigar or None, cigar_stride, stream or None))
+
+    # non-intersecting alignments over the six reading frames: every exon of a hit, best first
+    def align_disjoint_frame_hits(self, residues: np.ndarray, offsets: np.ndarray,
+                                  lens: np.ndarray, rounds: int, min_score: int = 1, hits=None,
+                                  hit_queries=None, hits_per_query: int = 0,
+                                  ids: Optional[np.ndarray] = None,
+                                  cigar_cap: Optional[int] = None, n_hits: Optional[int] = None,
+                                  codon_table=None) -> list:
+        """sw_align_disjoint_frame_hits: the pair list of align_set_hits over a host DNA batch;
+        for each hit a list of `rounds` Alignments, best first, merged from the non-intersecting
+        alignments of the query with each of the target's six translations (a tie goes to the
+        lowest frame).  Alignment.frame is the record's frame, t_start / t_end are nucleotides on
+        the forward target, the CIGAR runs in amino-acid columns.  Returns one list per hit."""
+        res, offs, ln, idv = validate_batch(residues, offsets, lens, ids)
+        tab = _codon_table(codon_table)
+        hv = None if hits is None else np.ascontiguousarray(hits, dtype=np.uint64).reshape(-1)
+        hq = None if hit_queries is None else \
+            np.ascontiguousarray(hit_queries, dtype=np.uint32).reshape(-1)
+        if n_hits is None:
+            n_hits = len(hv) if hv is not None else len(hq) if hq is not None else len(ln)
+        if (hv is not None and len(hv) < n_hits) or (hq is not None and len(hq) < n_hits):
+            raise ValueError("hits / hit_queries shorter than n_hits")
+        nrec = n_hits * max(int(rounds), 0)
+        out = np.zeros(max(nrec, 1), dtype=ALIGNMENT_DTYPE)
+        if cigar_cap is None:  # M runs alternate with gap runs, and an M run takes a row and a codon
+            tv = hv[:n_hits] if hv is not None else np.arange(min(n_hits, len(ln)), dtype=np.uint64)
+            sel = tv[tv < len(ln)].astype(np.int64)
+            per = 2 * np.minimum(ln[sel].astype(np.int64) // 3, DISJOINT_MAX_QUERY)
+            cigar_cap = max(int(rounds), 0) * int(per.sum()) + nrec
+        cig = np.zeros(max(cigar_cap, 1), dtype=np.uint32)
+        used = ctypes.c_size_t()
+        self._check(lib().sw_align_disjoint_frame_hits(
+            self._h, _p(res), res.size, _p(offs), _p(ln), _p(idv) if idv is not None else None,
+            len(ln), _p(tab) if tab is not None else None, rounds, min_score,
+            _p(hq) if hq is not None else None, hits_per_query,
+            _p(hv) if hv is not None else None, n_hits, _p(out), _p(cig) if cigar_cap else None,
+            cigar_cap, ctypes.byref(used)))
+        flat = alignments_from(out[:nrec], cig)
+        return [flat[h * rounds:(h + 1) * rounds] for h in range(n_hits)]
+
+    def align_disjoint_frame_hits_device(self, d_res: int, d_offs: int, d_lens: int, n: int,
+                                         max_len: int, rounds: int, n_hits: int, d_out: int,
+                                         min_score: int = 1, d_hits: int = 0,
+                                         d_hit_queries: int = 0, hits_per_query: int = 0,
+                                         d_cigar: int = 0, cigar_stride: int = 0, stream: int = 0,
+                                         d_ids: int = 0, codon_table=None):
+        """sw_align_disjoint_frame_hits_device: device pointers (ints), the pair list of
+        align_set_hits_device over the DNA batch score_frames_device scored; d_out receives
+        n_hits x rounds records, (hit h, round r) at h * rounds + r, its ops at
+        d_cigar + (h * rounds + r) * cigar_stride.  Async on `stream` (0: the bank's own stream;
+        sync() before reading)."""
+        tab = _codon_table(codon_table)
+        self._check(lib().sw_align_disjoint_frame_hits_device(
+            self._h, d_res or None, d_offs or None, d_lens or None, d_ids or None, n, max_len,
+            _p(tab) if tab is not None else None, rounds, min_score, d_hit_queries or None,
+            hits_per_query, d_hits or None, n_hits, d_out or None, d_cigar or None, cigar_stride,
+            stream or None))
 
     def estimate_frameshift_statistics_device(self, d_dna: int, d_offs: int, d_lens: int, n: int,
                                               max_len: int, frameshift: int, seed: int = 0,
